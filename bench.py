@@ -5,7 +5,9 @@
 training iteration over one synthetic batch resident in HBM: TimeSformer encoder forward, projection
 head + step logits + top-5 KL loss + global InfoNCE over the all-gathered clip / text embeddings,
 backward, gradient all-reduce (N > 1), fused AdamW step.
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").
+Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").  A plain run sets up, warms up, times the K steps and prints the
+line; `--full` adds the per-kernel roofline, CPU baseline, sustained leg, side lines and parity probe.  `--dump-outputs DIR`
+writes the last timed step's results as .npy files, for comparing two builds output for output.
 """
 import argparse
 import json
@@ -37,11 +39,11 @@ def main():
     ap.add_argument("--no-graphs", action="store_true", help="eager kernel launches instead of HIP-graph replay of the encoder")
     ap.add_argument("--no-wgrad-group", action="store_true", help="one launch per weight gradient instead of one per block")
     ap.add_argument("--no-side", action="store_true", help="skip the side measurements (configs[3] T=32 and configs[4] MViTv2-S) "
-                                                           "that the default single-GPU run appends to its JSON line")
+                                                           "that a --full single-GPU run appends to its JSON line")
     ap.add_argument("--all-sides", action="store_true", help="append the side lines (bf16 flavour, last block unpruned, full pre-training step, "
                                                              "configs[3] T = 32, configs[4] MViTv2-S) to a run that is not the default one")
     ap.add_argument("--sustained-steps", type=int, default=None,
-                    help="back-to-back steps of the `sustained` leg after the timed region (default: 300 on the default single-GPU run, else 0)")
+                    help="back-to-back steps of the `sustained` leg after the timed region (default: 300 on a --full single-GPU run, else 0)")
     ap.add_argument("--world1-rccl", action="store_true",
                     help="one GPU, but through the N > 1 machinery: a 1-rank RCCL process group, the per-block gradient hook between staged "
                          "HIP-graph replays, RCCL's all-reduce / all-gather kernels on its own stream (what the data-parallel path costs a rank)")
@@ -51,10 +53,21 @@ def main():
     ap.add_argument("--from-host", action="store_true",
                     help="PCIe-inclusive variant (DESIGN section 5; never the headline `value`): every step's clips start in pinned HOST memory "
                          "and are copied to one of two device buffers on a copy stream while the previous step computes")
-    ap.add_argument("--no-parity-probe", action="store_true", help="skip the 2-clip parity probe that the default run and every --gpus N run append")
+    ap.add_argument("--no-parity-probe", action="store_true", help="skip the 2-clip parity probe that --full appends to the default run and every --gpus N run")
     ap.add_argument("--arch", default="vit", choices=["vit", "mvit"],
                     help="vit = TimeSformer ViT-B, the BASELINE metric (configs[1]); mvit = MViTv2-S 16x224^2 (configs[4], side number)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline figure: the per-kernel timing / roofline leg, the CPU baseline, the "
+                         "sustained leg, the side lines and the 2-clip parity probe (a plain run: set-up, warm-up, the timed steps, "
+                         "the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): loss, step "
+                         "logits, clip embeddings, and fixed seeded samples of the updated parameters and of their gradients")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run measures the headline and nothing else; the legs below stay reachable one by one through their own options
+        args.no_kernel_timing = args.no_cpu_baseline = args.no_side = True
+        args.no_parity_probe = args.no_parity_probe or not args.parity_probe
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: become N ranks, one process per GPU (the reference's launch_job spawns one
@@ -178,6 +191,8 @@ def main():
                 staged["ev"] = copy_stream.record_event()
         stage()
 
+    last = {}
+
     def step():
         optimizer.zero_grad(set_to_none=True)
         if args.from_host:
@@ -187,6 +202,7 @@ def main():
             stage()
         else:
             pred = model(frames)
+        last["pred"] = pred
         loss = kl_topk_loss(pred, teacher, 5)                                # step matching (tools/train_net.py:152-160)
         v = vt.last_video_emb                                                # unit-norm clip embeddings [B, 512]
         v_all, t_all = (AllGather.apply(v), AllGather.apply(text_emb)) if dp_path else (v, text_emb)
@@ -232,7 +248,7 @@ def main():
         if k in timing_steps:
             ops.KERNEL_TIMING = timed_events
             vt.engine.use_graphs = False
-        loss = step()
+        loss, pred = step(), last["pred"]
         if k in timing_steps:
             ops.KERNEL_TIMING = None
             vt.engine.use_graphs = graphs
@@ -247,6 +263,8 @@ def main():
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
+    if args.dump_outputs and rank == 0:     # now, before any further step (sustained / isolated legs) overwrites the graphs' buffers
+        dump_outputs(args.dump_outputs, model, loss, pred, vt.last_video_emb)
     ops.KERNEL_TIMING = timed_events if timing_steps else None
     timing = ops.collect_kernel_timing() if timing_steps else None
     ops.KERNEL_TIMING = None
@@ -393,7 +411,8 @@ def main():
             torch.cuda.synchronize()
             if hasattr(vt.engine, "release_graphs"):
                 vt.engine.release_graphs()
-            del model, vt, optimizer, reducer, frames, teacher
+            last.clear()
+            del model, vt, optimizer, reducer, frames, teacher, pred
             gc.collect()
             torch.cuda.synchronize()
             torch.cuda.empty_cache()
@@ -438,6 +457,32 @@ def parity_probe(arch="vit", frames=8):
             "sample": f"{2 if frames <= 8 else 1} clip(s) of {frames} x 224^2, full-size model, one training step vs oracle/timesformer_oracle.py (fp32 CPU)"}
 
 
+def dump_outputs(out_dir, model, loss, pred, video_emb, sample=1 << 21):
+    """--dump-outputs: the last timed step's results as float32 .npy files -- the loss, the step logits [B, K], the unit-norm clip
+    embeddings [B, 512], and the same `sample` positions (seeded, fixed for a given model) of every trainable parameter after the
+    optimizer step and of its gradient, concatenated in named_parameters() order.  Any array over 4M elements is sampled the same way;
+    the whole dump stays under 64 MB."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    params = [p for _, p in model.named_parameters() if p.requires_grad]
+    flat = torch.cat([p.detach().reshape(-1).float() for p in params])
+    grads = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float() for p in params])
+
+    def pick(t, n):
+        t = t.detach().reshape(-1).float() if t.numel() > n else t.detach().float()
+        if t.numel() > n:
+            idx = torch.randint(t.numel(), (n,), generator=torch.Generator().manual_seed(0)).sort()[0]
+            t = t[idx.to(t.device)]
+        return t.cpu().numpy().astype(np.float32)
+
+    arrays = {"loss": loss.detach().float().reshape(1).cpu().numpy(), "logits": pick(pred, 1 << 22),
+              "video_emb": pick(video_emb, 1 << 22), "params_sample": pick(flat, sample), "grads_sample": pick(grads, sample)}
+    del flat, grads
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def side_measurements(all_sides=False):
     """The other single-GPU lines, each a child process of this same script under the driver's clock: configs[1] with bf16 operands
     (the type BASELINE's configs name; not held to 1e-3), configs[1] with the last block unpruned, and the reference's full pre-training
@@ -445,7 +490,7 @@ def side_measurements(all_sides=False):
     and configs[4], whose per-kernel profiles are tracked under profiles/."""
     import subprocess
     res = []
-    base = ["--no-cpu-baseline", "--no-side"]
+    base = ["--full", "--no-cpu-baseline", "--no-side"]
     full = os.path.join(ROOT, "tools", "bench_full_step.py")
     lines = [
         ("configs[1] with bf16 operands (PVRL_OPERAND=bf16, libpvrl_hip.so): TimeSformer ViT-B 8x224^2, 32 clips/GPU",

@@ -1,6 +1,6 @@
 """Generate the golden fixtures under tests/golden/ by running the UNMODIFIED reference modules.
 
-Run in the build container only (needs /root/reference; it is skipped by the tests when absent):
+Run where a reference checkout is available (REF below); the tests read only the fixtures it writes:
     python tests/golden/make_golden.py
 The reference package cannot be imported as shipped (lib/models/optimizer.py:40-41 SyntaxError,
 lib/models/video_model_builder.py:23 bad import, lib/models/tfm_model.py:3 `from turtle import distance`, fvcore /
@@ -336,6 +336,62 @@ def make_lr_table(defaults, out):
         eps = [e / 4.0 for e in range(0, 4 * int(cfg.SOLVER.MAX_EPOCH))]
         tab[name] = dict(epochs=eps, lrs=[lrp.get_lr_at_epoch(cfg, e) for e in eps])
     out["lr_table"] = tab
+
+
+def make_reference_configs(out):
+    """The eight yaml files under the reference's configs/, as the mappings yaml.safe_load reads from them (values only: no comments),
+    keyed by their path relative to configs/ -- what the config surface must accept unchanged."""
+    import glob
+    files = sorted(glob.glob(os.path.join(REF, "configs", "*", "*.yaml")))
+    out["reference_configs"] = {os.path.relpath(f, os.path.join(REF, "configs")): yaml.safe_load(open(f)) for f in files}
+
+
+class _PathManager:
+    exists = staticmethod(os.path.exists)
+    ls = staticmethod(os.listdir)
+    isfile = staticmethod(os.path.isfile)
+
+    @staticmethod
+    def mkdirs(p):
+        os.makedirs(p, exist_ok=True)
+
+    @staticmethod
+    def open(p, mode="r"):
+        return open(p, mode)
+
+
+def import_reference_checkpoint():
+    """lib.utils.checkpoint (fvcore's PathManager stubbed by local file I/O); call after import_reference()"""
+    fio = types.ModuleType("fvcore.common.file_io")
+    fio.PathManager = _PathManager
+    sys.modules["fvcore.common.file_io"] = fio
+    return importlib.import_module("lib.utils.checkpoint")
+
+
+CKPT_SEED = 23
+
+
+def make_checkpoint(defaults, vit, tfm, out, tmpdir):
+    """A `.pyth` written by the reference's save_checkpoint (epoch 4, SGD) for the 1-block, 32^2, K = 16 model with a 1-layer text tower,
+    its weights set to seeded_state(CKPT_SEED).  Stored without the tensor payloads (regenerated by name from the seed, like every fixture
+    here): the file's path under the job directory, its top-level keys in order, the epoch, the optimizer state, the cfg dump, and the
+    model_state's keys in order with shape and dtype."""
+    ck = import_reference_checkpoint()
+    cfg, model, _ = build_ref_model(defaults, vit, tfm, depth=1, crop=32, K=16, text_layers=1, tmpdir=tmpdir)
+    sd = load_seeded(model, CKPT_SEED)
+    cfg.TRAIN.CHECKPOINT_PERIOD = 1
+    opt = torch.optim.SGD([p for p in model.parameters() if p.requires_grad], lr=0.1, momentum=0.9)
+    job = os.path.join(tmpdir, "job_ref")
+    path = ck.save_checkpoint(job, model, opt, 4, cfg)
+    f = torch.load(path, map_location="cpu", weights_only=False)
+    ms = f["model_state"]
+    assert list(ms) == list(model.state_dict()) and set(ms) == set(sd)
+    for k, v in ms.items():
+        assert torch.equal(v, sd[k].to(v.dtype)), k
+    out["checkpoint"] = dict(seed=CKPT_SEED, path=os.path.relpath(path, job), keys=list(f.keys()), epoch=f["epoch"],
+                             optimizer_state=f["optimizer_state"], cfg=f["cfg"],
+                             model_state=[(k, tuple(v.shape), str(v.dtype).replace("torch.", "")) for k, v in ms.items()],
+                             checksum=checksum(ms))
 
 
 def imagenet_vit_shapes(depth, num_patches=196, dim=768, classes=1000):
@@ -710,6 +766,18 @@ def main():
             torch.save(v, os.path.join(HERE, k + ".pt"))
             print("wrote", k, os.path.getsize(os.path.join(HERE, k + ".pt")) // 1024, "KiB")
         return
+    if len(sys.argv) > 2 and sys.argv[1] == "--only" and sys.argv[2] in ("reference_configs", "checkpoint"):
+        out = {}
+        if sys.argv[2] == "reference_configs":
+            make_reference_configs(out)
+        else:
+            defaults, vit, tfm, dist_mod, losses = import_reference()
+            with tempfile.TemporaryDirectory() as tmp:
+                make_checkpoint(defaults, vit, tfm, out, tmp)
+        k = sys.argv[2]
+        torch.save(out[k], os.path.join(HERE, k + ".pt"))
+        print("wrote", k, os.path.getsize(os.path.join(HERE, k + ".pt")) // 1024, "KiB")
+        return
     if len(sys.argv) > 2 and sys.argv[1] == "--only" and sys.argv[2] == "input_pipeline":
         _install_stubs()
         out = {}
@@ -729,6 +797,9 @@ def main():
         make_mvit_e2e(defaults, tfm, out, tmp)
     make_small_ops(vit, losses, out)
     make_lr_table(defaults, out)
+    make_reference_configs(out)
+    with tempfile.TemporaryDirectory() as tmp:
+        make_checkpoint(defaults, vit, tfm, out, tmp)
     make_allgather(dist_mod, out)
     make_input_pipeline(out)
     make_mvit(defaults, out)

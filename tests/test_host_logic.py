@@ -8,7 +8,6 @@ import torch
 
 from procedurevrl_amd.config import CfgNode, get_cfg
 
-REF_CFG = "/root/reference/configs"
 
 
 def test_cfg_defaults_and_overrides():
@@ -27,9 +26,14 @@ def test_cfg_defaults_and_overrides():
         cfg.NUM_GPUS = 3
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="reference configs not present")
-def test_reference_yaml_files_load_unchanged():
-    files = sorted(glob.glob(os.path.join(REF_CFG, "*", "*.yaml")))
+def test_reference_yaml_files_load_unchanged(tmp_path):
+    # the reference's eight configs/*/*.yaml, as yaml.safe_load reads them (tests/golden/make_golden.py), written back out as yaml files
+    import yaml
+    ref = torch.load(os.path.join(os.path.dirname(__file__), "golden", "reference_configs.pt"), weights_only=False)
+    for rel, mapping in ref.items():
+        os.makedirs(tmp_path / os.path.dirname(rel), exist_ok=True)
+        (tmp_path / rel).write_text(yaml.safe_dump(mapping))
+    files = sorted(glob.glob(os.path.join(tmp_path, "*", "*.yaml")))
     assert len(files) == 8
     for f in files:
         cfg = get_cfg()
@@ -37,7 +41,7 @@ def test_reference_yaml_files_load_unchanged():
         assert cfg.TIMESFORMER.ATTENTION_TYPE == "divided_space_time"
         assert isinstance(cfg.SOLVER.BASE_LR, float) and isinstance(cfg.SOLVER.WEIGHT_DECAY, float)
     cfg = get_cfg()
-    cfg.merge_from_file(os.path.join(REF_CFG, "HowTo100M", "procedurevrl_mvitv2_adamw.yaml"))
+    cfg.merge_from_file(os.path.join(tmp_path, "HowTo100M", "procedurevrl_mvitv2_adamw.yaml"))
     assert cfg.MVIT.PATCH_KERNEL == [3, 7, 7] and cfg.MVIT.PATCH_STRIDE == [2, 4, 4]   # "(3, 7, 7)" strings literal_eval'ed
 
 

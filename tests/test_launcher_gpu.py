@@ -121,7 +121,7 @@ def test_bench_spawns_its_own_ranks():
     env = dict(os.environ, PVRL_DIST_BACKEND="gloo", PVRL_SINGLE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "2", "--steps", "2",
-                        "--warmup", "1", "--classes", "512", "--no-cpu-baseline"], capture_output=True, text=True, env=env,
+                        "--warmup", "1", "--classes", "512", "--full", "--no-cpu-baseline"], capture_output=True, text=True, env=env,
                        timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -148,7 +148,7 @@ def test_bench_eight_ranks_the_drivers_command():
         env.pop(k, None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--batch", "2", "--steps", "2",
-                        "--warmup", "1", "--classes", "512", "--no-cpu-baseline", "--no-kernel-timing"],
+                        "--warmup", "1", "--classes", "512", "--full", "--no-cpu-baseline", "--no-kernel-timing"],
                        capture_output=True, text=True, env=env, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -30,7 +30,7 @@ def test_bench_two_ranks_over_rccl():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("PVRL_SINGLE_DEVICE", None); env.pop("PVRL_DIST_BACKEND", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "4", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-side", "--no-kernel-timing"], capture_output=True, text=True, timeout=900, env=env)
+                        "--full", "--no-cpu-baseline", "--no-side", "--no-kernel-timing"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     print("RCCL", d["comm"])

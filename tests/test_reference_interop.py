@@ -1,43 +1,26 @@
-"""Checkpoint interop against the REFERENCE's own save / load code (lib/utils/checkpoint.py), run in the build container
-only (skipped where /root/reference is absent, e.g. on the GPU box): a `.pyth` written by the reference loads into this
-implementation and vice versa, with identical tensors.  No GPU needed: state_dict plumbing only."""
+"""Checkpoint interop with the REFERENCE's own save / load code (lib/utils/checkpoint.py), pinned by tests/golden/checkpoint.pt: a `.pyth`
+written by the reference's save_checkpoint loads into this implementation with identical tensors, and a `.pyth` written here has the
+layout the reference's load_checkpoint reads (every model_state key of the reference model with its shape and dtype, so that nothing is
+left "not loaded", and the epoch it returns).  The fixture stores the reference file without its tensor payloads: the weights are
+seeded_state(seed) by name, as in every fixture here (tests/golden/make_golden.py).  No GPU needed: state_dict plumbing only."""
 import os
-import sys
-import types
+from collections import OrderedDict
 
-import pytest
 import torch
 
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
+from oracle import timesformer_oracle as orc
+
+GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 
 
-class _PathManager:
-    exists = staticmethod(os.path.exists)
-    ls = staticmethod(os.listdir)
-    isfile = staticmethod(os.path.isfile)
-
-    @staticmethod
-    def mkdirs(p):
-        os.makedirs(p, exist_ok=True)
-
-    @staticmethod
-    def open(p, mode="r"):
-        return open(p, mode)
-
-
-@pytest.fixture(scope="module")
-def ref():
-    sys.dont_write_bytecode = True
-    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
-    import make_golden as mg
-    defaults, vit, tfm, dist_mod, losses = mg.import_reference()
-    fio = types.ModuleType("fvcore.common.file_io")
-    fio.PathManager = _PathManager
-    sys.modules["fvcore.common.file_io"] = fio
-    import importlib
-    ck = importlib.import_module("lib.utils.checkpoint")
-    return types.SimpleNamespace(mg=mg, defaults=defaults, vit=vit, tfm=tfm, ck=ck)
+def _ref_checkpoint():
+    g = torch.load(os.path.join(GOLDEN, "checkpoint.pt"), weights_only=False)
+    shapes = {k: shp for k, shp, _ in g["model_state"]}
+    sd = orc.seeded_state(shapes, g["seed"])
+    ms = OrderedDict((k, sd[k].to(getattr(torch, dt))) for k, _, dt in g["model_state"])
+    assert abs(float(sum(v.double().abs().sum() for v in ms.values())) - g["checksum"]) <= 1e-9 * g["checksum"]
+    body = {"epoch": g["epoch"], "model_state": ms, "optimizer_state": g["optimizer_state"], "cfg": g["cfg"]}
+    return g, OrderedDict((k, body[k]) for k in g["keys"])
 
 
 def _my_model(cfg_ref, label_path):
@@ -54,23 +37,28 @@ def _my_model(cfg_ref, label_path):
     return cfg, MODEL_REGISTRY.get(cfg.MODEL.MODEL_NAME)(cfg)
 
 
-def test_reference_checkpoint_loads_here_and_ours_loads_there(ref, tmp_path):
+def test_reference_checkpoint_loads_here_and_ours_loads_there(tmp_path):
     from procedurevrl_amd import checkpoint as cu
-    cfg_r, model_r, _ = ref.mg.build_ref_model(ref.defaults, ref.vit, ref.tfm, depth=1, crop=32, K=16, text_layers=1,
-                                               tmpdir=str(tmp_path))
-    cfg_r.TRAIN.CHECKPOINT_PERIOD = 1
-    opt_r = torch.optim.SGD([p for p in model_r.parameters() if p.requires_grad], lr=0.1, momentum=0.9)
-    path = ref.ck.save_checkpoint(str(tmp_path / "job_ref"), model_r, opt_r, 4, cfg_r)
-    assert path.endswith("checkpoints/checkpoint_epoch_00005.pyth")
-    cfg_m, model_m = _my_model(cfg_r, cfg_r.TRAIN.LABEL_EMB)
+    from procedurevrl_amd.config import CfgNode
+    g, ck_r = _ref_checkpoint()
+    assert g["path"] == os.path.join("checkpoints", "checkpoint_epoch_00005.pyth")
+    path = str(tmp_path / "job_ref" / g["path"])
+    os.makedirs(os.path.dirname(path))
+    torch.save(ck_r, path)
+    cfg_r = CfgNode.load_cfg(g["cfg"])
+    K = cfg_r.MODEL.NUM_CLASSES
+    label_path = str(tmp_path / "label_emb.pth")
+    torch.save(torch.nn.functional.normalize(torch.randn(K, 512), dim=1), label_path)
+    cfg_m, model_m = _my_model(cfg_r, label_path)
     # same key set on both sides (the text tower is part of the reference's state_dict as well)
-    assert set(model_m.state_dict().keys()) == set(model_r.state_dict().keys())
+    assert set(model_m.state_dict().keys()) == set(ck_r["model_state"].keys())
     epoch = cu.load_checkpoint(path, model_m, data_parallel=False, optimizer=None)
     assert epoch == 4
-    sr, sm = model_r.state_dict(), model_m.state_dict()
+    sr, sm = ck_r["model_state"], model_m.state_dict()
     for k in sr:
         assert torch.equal(sr[k], sm[k]), k
-    # ... and back: a checkpoint written here, read by the reference's load_checkpoint
+    # ... and back: a checkpoint written here, in the layout the reference's load_checkpoint reads -- it copies every model_state entry
+    # whose key and shape match its model's, and returns `epoch`
     from procedurevrl_amd.optimizer import construct_optimizer
     with torch.no_grad():
         for p in model_m.parameters():
@@ -80,8 +68,12 @@ def test_reference_checkpoint_loads_here_and_ours_loads_there(ref, tmp_path):
     assert os.path.basename(path2) == "checkpoint_epoch_00008.pyth"
     ck = torch.load(path2, map_location="cpu", weights_only=False)
     assert set(ck.keys()) == {"epoch", "model_state", "optimizer_state", "cfg"}
-    epoch_r = ref.ck.load_checkpoint(path2, model_r, data_parallel=False, optimizer=None)
-    assert epoch_r == 7
-    sr, sm = model_r.state_dict(), model_m.state_dict()
+    assert ck["epoch"] == 7
+    ref_layout = {k: (tuple(shp), dt) for k, shp, dt in g["model_state"]}
+    mine = ck["model_state"]
+    assert set(mine) == set(ref_layout)
+    for k, v in mine.items():
+        assert (tuple(v.shape), str(v.dtype).replace("torch.", "")) == ref_layout[k], k
+    sm = model_m.state_dict()
     for k in sm:
-        assert torch.equal(sr[k], sm[k]), k
+        assert torch.equal(mine[k], sm[k]), k

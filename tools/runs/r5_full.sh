@@ -7,7 +7,7 @@ grep -n "FAILED\|ERROR" gpurun_out/r5_suite_v.txt | head -20 >> $O
 grep -n -B2 -A12 "Fatal Python\|Segmentation" gpurun_out/r5_suite_v.txt | head -40 >> $O
 tail -3 gpurun_out/r5_suite_v.txt >> $O
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -3 >> $O
-( time python bench.py ) > gpurun_out/r5_bench_default.json 2> gpurun_out/r5_bench_default.err; echo "bench rc=$?" >> $O
+( time python bench.py --full ) > ${O%/*}/r5_bench_default.json 2> ${O%/*}/r5_bench_default.err; echo "bench rc=$?" >> $O
 tail -4 gpurun_out/r5_bench_default.err >> $O
 python - >> $O <<'PY'
 import json
