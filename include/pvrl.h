@@ -11,7 +11,8 @@
  * Conventions
  *   - plain pointers to DEVICE memory + sizes; no torch types.  `stream` is a hipStream_t.
  *   - the caller owns every buffer, including workspaces; nothing is allocated, nothing
- *     synchronises, no global state; every call is asynchronous on `stream`.
+ *     synchronises; every call is asynchronous on `stream`.  The one piece of process-wide state is the
+ *     PVRL_COMPUTE_CUS environment variable (CUs per XCD the persistent kernels size their grids for), read once.
  *   - return 0 on success, PVRL_EINVAL (-1) on a bad argument, <= -2 on a HIP launch error.
  *   - "bf16" in entry-point names, PVRL_EPI_* names and comments means THE LIBRARY'S 16-BIT OPERAND TYPE: fp16 in the default
  *     library (libpvrl_hip_f16.so, what procedurevrl_amd loads unless PVRL_OPERAND=bf16 -- the flavour that meets the 1e-3 parity
@@ -190,8 +191,8 @@ int pvrl_attn_t8_bwd(const void* qkv, int64_t ld, int64_t nseq, int64_t H, float
  * tfm_model.py:43-48 with key_padding_mask; CLIP text causal mask).  S <= 416 without masks (the reference takes any crop
  * through its pos-embed resize, vit.py:374-386: 224^2 -> 197 tokens, 256^2 -> 257, 320^2 -> 401), S <= 208 with a causal /
  * key-padding mask; PVRL_EINVAL beyond.  The backward of 96 < S <= 224 without masks and with a power-of-two `scale` is ONE
- * persistent kernel (csrc/attn_bwd_fused.hip; PVRL_ATTN_BWD_FUSED=0 selects the two-pass kernels), that of 16 < S <= 32 contiguous
- * tokens one wave per (sequence, head) (csrc/attn_bwd_s32.hip; PVRL_ATTN_BWD_S32=0); `dvec` is then unused.
+ * persistent kernel (csrc/attn_bwd_fused.hip), that of 16 < S <= 32 contiguous tokens one wave per (sequence, head)
+ * (csrc/attn_bwd_s32.hip); `dvec` is then unused.
  * mode 0: row(seq, j) = seq*S + j.   mode 1 (TimeSformer spatial, seq = b*T + t): token 0 = cls row
  * cls_base + b, token j>=1 = row b*(S-1)*T + (j-1)*T + t; token-0 outputs go to the *_cls side buffers
  * ([nseq] rows).  lse/dvec: [nseq][H][S] fp32. */

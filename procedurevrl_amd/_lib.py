@@ -19,7 +19,7 @@ OPERAND = os.environ.get("PVRL_OPERAND", "f16").lower()
 if OPERAND not in ("bf16", "f16"):
     raise RuntimeError(f"PVRL_OPERAND={OPERAND!r}: expected 'f16' or 'bf16'")
 LIB_PATH = os.path.join(_HERE, "csrc", "libpvrl_hip.so" if OPERAND == "bf16" else "libpvrl_hip_f16.so")
-# A/B runs of a differently-built library (tools/build_variant.py: same sources, extra -D switches); never set in production
+# A/B runs against another build of the library (e.g. the parent commit's libpvrl_hip*.so); never set in production
 LIB_PATH = os.environ.get("PVRL_LIB_PATH", LIB_PATH)
 
 

@@ -40,41 +40,12 @@
 
 namespace {
 
-#ifndef PVRL_FB_TRACE
-#define PVRL_FB_TRACE 0       // probe builds only: every wave of workgroup 8 stamps the cycle counter at the seams of each block of its
-#endif                        // SECOND item into spare LDS; dumped through AttnArgs::dvec (tools/probe/attn_bwd_ab.py trace)
-#ifndef PVRL_FB_PRIO7
-#define PVRL_FB_PRIO7 3
-#endif
-#ifndef PVRL_FB_PRIO46
-#define PVRL_FB_PRIO46 1
-#endif
-#ifndef PVRL_FB_ABLATE
-#define PVRL_FB_ABLATE 0      // probe builds only (results are garbage, only the dQ wave's time means something): 1 = no start values of streamed
-#endif                        // slots, 2 = no dQ staging / stores, 4 = no dQ MFMAs, 8 = no dQ fragment reads
+constexpr int FB_PRIO7 = 3, FB_PRIO46 = 1;    // s_setprio of the dQ wave (7) and of the younger wave of each SIMD pair (4-6)
 constexpr int FB_DS = FB_ROWS * 64;          // dS^T image of one query block: [224 keys][32 queries]
 constexpr int FB_Q = 0, FB_D = FB_TILE, FB_K = 2 * FB_TILE, FB_S = 4 * FB_TILE, FB_INIT = 4 * FB_TILE + 2 * FB_DS;
 constexpr int FB_O = FB_INIT + 4 * FB_ROWS * 4;         // {-lse/scale, -D*scale} x two items, then the O ring: 3 slots of 32 rows
 constexpr int FB_LSE = FB_O + 3 * 4096;                 // lse of the ring's rows: 3 x 64 floats
 constexpr int FB_LDS = FB_LSE + 3 * 256;
-
-#if PVRL_FB_TRACE
-#define FB_STAMP(jb, k)                                                                                                   \
-  do {                                                                                                                    \
-    if (tracing) reinterpret_cast<unsigned*>(smem + FB_LDS)[(wave * 8 + (jb)) * 8 + (k)] = (unsigned)__builtin_readcyclecounter(); \
-  } while (0)
-#define FB_TRACE_DUMP()                                                                                                    \
-  do {                                                                                                                     \
-    if (tracing && p.dvec) {                                                                                               \
-      FB_STAMP(7, 4);                                                                                                      \
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                   \
-      reinterpret_cast<unsigned*>(p.dvec)[wave * 64 + lane] = reinterpret_cast<unsigned*>(smem + FB_LDS)[wave * 64 + lane]; \
-    }                                                                                                                      \
-  } while (0)
-#else
-#define FB_STAMP(jb, k) do { } while (0)
-#define FB_TRACE_DUMP() do { } while (0)
-#endif
 
 // One of the 13 copies that bring rows 32jb .. 32jb+31 of the next item in: o = 0..3 Q pieces, 4..7 dO pieces (both into the freed
 // slots of the images), 8..11 O pieces and 12 the rows' lse (ring slot rs).  `o` is wave-uniform and fixed per wave, so everything
@@ -178,7 +149,6 @@ __device__ __forceinline__ void dq_block(const AttnArgs& p, const FbItem& it, co
   const int b0 = (2 * g) * 256 + hi * 128 + (i >> 2) * 32 + (((i & 3) ^ (2 * g)) * 8);      // dS^T image
   const int b1 = (2 * g + 1) * 256 + hi * 128 + (i >> 2) * 32 + (((i & 3) ^ (2 * g + 1)) * 8);
   auto load = [&](int ks, opx8& bf, opx8* af) {
-    if (PVRL_FB_ABLATE & 8) { bf = (opx8){}; af[0] = af[1] = (opx8){}; return; }
     bf = tr_frag8(dsr + ks * 1024, b0, b1);
 #pragma unroll
     for (int dh = 0; dh < 2; ++dh) af[dh] = tr_frag8(Kb + ks * 2048 + dh * 256, a0, a1);
@@ -195,7 +165,6 @@ __device__ __forceinline__ void dq_block(const AttnArgs& p, const FbItem& it, co
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int dh = 0; dh < 2; ++dh) {
-        if (PVRL_FB_ABLATE & 4) { acc[dh][0] += (float)af[ks % 3][dh][0] + (float)bf[ks % 3][1]; continue; }
         acc[dh] = MFMA_32x32x16(af[ks % 3][dh], bf[ks % 3], acc[dh], 0, 0, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -214,7 +183,6 @@ __device__ __forceinline__ void dq_block(const AttnArgs& p, const FbItem& it, co
   // only reader of the block's dS^T buffer and is done with it: transpose through it ([query][64 columns], 16-byte chunks swizzled by
   // the query) and store whole 128-byte rows, 8 rows per instruction.
   char* st = const_cast<char*>(dsr);
-  if (PVRL_FB_ABLATE & 2) { if (acc[0][0] + acc[1][0] == 12345.f) st[lane] = 1; return; }
   {
     const int q = lane & 31;
 #pragma unroll
@@ -239,7 +207,7 @@ __device__ __forceinline__ void dq_block(const AttnArgs& p, const FbItem& it, co
 
 template <int NQB>
 __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p, int nvb) {
-  __shared__ __attribute__((aligned(16))) char smem[FB_LDS + (PVRL_FB_TRACE ? 8 * 8 * 8 * 4 : 0)];
+  __shared__ __attribute__((aligned(16))) char smem[FB_LDS];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int S = p.mp.S;
@@ -249,9 +217,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p, int 
   const bool keywave = wave < nqb;
   const float c = p.scale * 1.4426950408889634f;
   const unsigned ldsbase = __builtin_amdgcn_readfirstlane(lds_addr(smem));
-#if PVRL_FB_TRACE
-  bool tracing = false;
-#endif
 
   FbItem cur, nxt;
   int vcur = -1;
@@ -271,29 +236,20 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p, int 
     // =========================================================== the dQ wave (and the start values of the streamed slots)
     // It is the youngest wave of its SIMD and the critical path of a block: without priority its VALU work (start values, store
     // addresses) only gets the issue slots its partner leaves (MI355X_MICROARCH: arbitration by priority, then age).
-    __builtin_amdgcn_s_setprio(PVRL_FB_PRIO7);
+    __builtin_amdgcn_s_setprio(FB_PRIO7);
     while (true) {
       if (vcur >= 0) {
 #pragma unroll 1
         for (int jb = 0; jb < nqb; ++jb) {
-          FB_STAMP(jb, 0);
           FB_BARRIER();
-          FB_STAMP(jb, 1);
-          FB_STAMP(jb, 2);
           dq_block<NQB>(p, cur, smem + FB_K + par * FB_TILE, smem + FB_S + (jb & 1) * FB_DS, nqb, S, jb, lane);
-          FB_STAMP(jb, 3);
         }
       }
-      FB_TRACE_DUMP();
       if (vnxt < 0) break;
       FB_BARRIER();                  // item seam
       par ^= 1; ++nit;
       cur = nxt; vcur = vnxt;
       vnxt = fb_next(p, vcur + gridDim.x, gridDim.x, nvb, nxt);
-#if PVRL_FB_TRACE
-      tracing = blockIdx.x == 8 && nit == 1;
-      FB_STAMP(7, 0);
-#endif
     }
     return;
   }
@@ -315,7 +271,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p, int 
   // waves' LDS / address-pipe work that bounds it, not who issues it.  `ncp` is also the vmcnt a wave allows in flight at a barrier.
   const int ncp = wave < 4 ? 3 : (wave == 4 ? 1 : 0);
   const FbCopy cp1 = fb_copy_init(wave < 4 ? wave : 12, lane), cp2 = fb_copy_init(4 + (wave & 3), lane), cp3 = fb_copy_init(8 + (wave & 3), lane);
-  if (wave >= 4) __builtin_amdgcn_s_setprio(PVRL_FB_PRIO46);      // the younger wave of each SIMD pair
+  if (wave >= 4) __builtin_amdgcn_s_setprio(FB_PRIO46);      // the younger wave of each SIMD pair
   opx8 kf[4], vf[4];
   f32x16 dk[2], dvv[2];
   while (true) {
@@ -345,9 +301,8 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p, int 
 #pragma unroll 1
       for (int jb = 0; jb < nqb; ++jb) {
         char* dsj = smem + FB_S + (jb & 1) * FB_DS;
-        FB_STAMP(jb, 0);
         // start values of a streamed slot: the one sent three blocks ago has landed (every sender waited for it before the last barrier)
-        if (wave < 4 && !(PVRL_FB_ABLATE & 1)) {
+        if (wave < 4) {
           if (jb >= 3) {
             if (vnxt >= 0)
               fb_finalize_quarter(smem, jb - 3, (nqb * nit + jb - 3) % 3, wave, S, p.scale, lane,
@@ -378,7 +333,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p, int 
             const opx8 da = *reinterpret_cast<const opx8*>(Dj + ((s & 1) ? e1 : e0) + 256 * (s >> 1));
             dacc = MFMA_32x32x16(da, vf[s], dacc, 0, 0, 0);
           }
-          FB_STAMP(jb, 1);
           // rows of block jb - 1 are dead since the last barrier: the next item's rows move in, addressed and issued under the MFMAs above
           if (vnxt >= 0 && jb >= 1) {
             const int rs = (nqb * nit + jb - 1) % 3;
@@ -394,7 +348,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p, int 
             pf[r >> 3][r & 7] = (op_t)pr;
             sf[r >> 3][r & 7] = (op_t)dsv;
           }
-          FB_STAMP(jb, 2);
 #pragma unroll
           for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -419,16 +372,14 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p, int 
           if (ncp >= 1) fb_slot_op(p, nxt, jb - 1, cp1, rs, S, ldsbase);
           if (ncp >= 3) { fb_slot_op(p, nxt, jb - 1, cp2, rs, S, ldsbase); fb_slot_op(p, nxt, jb - 1, cp3, rs, S, ldsbase); }
         }
-        FB_STAMP(jb, 3);
         // this wave's copies of the block before the last have landed (at most the newest slot's are in flight)
         if (ncp >= 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
         else if (ncp >= 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         FB_BARRIER();
-        FB_STAMP(jb, 4);
       }
       // start values of slot nqb - 3 (the next item's block loop finishes nqb - 2 and nqb - 1)
-      if (wave < 4 && vnxt >= 0 && !(PVRL_FB_ABLATE & 1))
+      if (wave < 4 && vnxt >= 0)
         fb_finalize_quarter(smem, nqb - 3, (nqb * nit + nqb - 3) % 3, wave, S, p.scale, lane,
                             reinterpret_cast<float*>(smem + FB_INIT) + (par ^ 1) * 2 * FB_ROWS);
       // the last block's rows (the other slots were sent from inside the following block, under its first MFMAs)
@@ -479,16 +430,11 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p, int 
         }
       }
     }
-    FB_TRACE_DUMP();
     if (vnxt < 0) break;
     FB_BARRIER();                    // item seam (all eight waves)
     par ^= 1; ++nit;
     cur = nxt; vcur = vnxt;
     vnxt = fb_next(p, vcur + gridDim.x, gridDim.x, nvb, nxt);
-#if PVRL_FB_TRACE
-    tracing = blockIdx.x == 8 && nit == 1;
-    FB_STAMP(7, 0);
-#endif
     // this wave's K rows from the fresh image (a row fragment per column step), its V rows from the prefetch registers
     {
       const char* Kc = smem + FB_K + par * FB_TILE + wave * 4096;

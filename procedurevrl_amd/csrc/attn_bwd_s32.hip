@@ -19,15 +19,11 @@
 // `scale` must be a power of two (folded into the V operand and into D, exactly).
 #include "attn_stream.h"
 #include "../../include/pvrl.h"
-#include <stdlib.h>
 
 namespace {
 
 constexpr int S32_WAVE_LDS = 3 * 4096 + 2048;      // Q, dO, K images (32 rows x 128 B) + the dS^T image / D values
-#ifndef PVRL_S32_NW
-#define PVRL_S32_NW 2                              // waves (= items) per workgroup (the waves never synchronise): 28 KB of LDS, five workgroups per CU; 1 / 3 / 4 measured 150 / 146 / 152 us against 144
-#endif
-constexpr int S32_NW = PVRL_S32_NW;
+constexpr int S32_NW = 2;      // waves (= items) per workgroup (the waves never synchronise): 28 KB of LDS, five workgroups per CU; 1 / 3 / 4 measured 150 / 146 / 152 us against 144
 
 __global__ __launch_bounds__(64 * S32_NW) void attn_bwd_s32_kernel(AttnArgs p) {
   __shared__ __attribute__((aligned(16))) char smem[S32_NW * S32_WAVE_LDS];
@@ -187,20 +183,10 @@ __global__ __launch_bounds__(64 * S32_NW) void attn_bwd_s32_kernel(AttnArgs p) {
   emit(dq, Ki, 0);
 }
 
-// PVRL_ATTN_BWD_S32=0 sends the short sequences back to the two-pass kernels (A/B runs); read once
-int attn_bwd_s32_enabled() {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("PVRL_ATTN_BWD_S32");
-    on = e ? (e[0] == '0' ? 0 : 1) : 1;
-  }
-  return on;
-}
-
 }  // namespace
 
 bool pvrl_attn_bwd_s32_ok(const AttnArgs& p) {
-  if (!attn_bwd_s32_enabled() || p.causal || p.kpm || p.mp.mode != 0) return false;
+  if (p.causal || p.kpm || p.mp.mode != 0) return false;
   if (p.mp.S <= 16 || p.mp.S > 32) return false;
   if ((p.ldd % 8) || (p.ldo % 8)) return false;                        // 16-byte row accesses
   int e = 0;

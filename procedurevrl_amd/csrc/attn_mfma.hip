@@ -26,7 +26,6 @@
 // straight-line code the compiler can software-pipeline (a run-time tile count cost 5x in branches).
 #include "attn_common.h"
 #include "../../include/pvrl.h"
-#include <stdlib.h>
 
 // attn_bwd_fused.hip: the persistent, LDS-DMA-streamed one-kernel backward for 96 < S <= 224 without masks
 bool pvrl_attn_bwd_fused_ok(const AttnArgs& p);
@@ -36,16 +35,6 @@ bool pvrl_attn_bwd_s32_ok(const AttnArgs& p);
 int pvrl_attn_bwd_s32_launch(const AttnArgs& p, hipStream_t s);
 
 namespace {
-
-// PVRL_ATTN_BWD_FUSED=0 sends every case back to the two-pass kernels (A/B runs); read once
-int attn_bwd_fused_enabled() {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("PVRL_ATTN_BWD_FUSED");
-    on = e ? (e[0] == '0' ? 0 : 1) : 1;
-  }
-  return on;
-}
 
 // key-padding bits of the 4*NKT keys a lane owns in the "lane = query" layout (key = 16 kt + 4 q4 + r)
 template <int NKT, bool GEN>
@@ -81,20 +70,12 @@ __device__ __forceinline__ void tile_issue(TileRegs<NT, ROWS>& t, const op_t* ba
     // BRANCH-FREE: every lane loads (rows past the sequence re-read its last row) and the padding is zeroed by a select.  A load
     // inside `if (row < S)` is followed by s_waitcnt vmcnt(0) at the join: the two guarded iterations of
     // this loop cost the workgroup two extra serial memory round trips in front of its first barrier.
-#if defined(PVRL_ATTN_GUARDED_LOADS)      // A/B builds only: the round-1 form
-    t.v[it] = (u32x4){0u, 0u, 0u, 0u};
-    if (row < S && row < rows) {
-      const op_t* src = (row == 0 && src0) ? src0 : base + row_of(sr, row) * ld;
-      t.v[it] = *reinterpret_cast<const u32x4*>(src + col0 + c * 8);
-    }
-#else
     const int rc = min(row, S - 1);
     const op_t* src = (rc == 0 && src0) ? src0 : base + row_of(sr, rc) * ld;
     const u32x4 v = *reinterpret_cast<const u32x4*>(src + col0 + c * 8);
     const unsigned keep = row < S ? 0xffffffffu : 0u;
     t.v[it] = v & (u32x4){keep, keep, keep, keep};
     (void)rows;
-#endif
   }
 }
 template <int NT, int ROWS = ATT_ROWS_PAD>
@@ -501,13 +482,10 @@ int check_common(const AttnArgs& p) {
 // long clips) -- are instantiated with S as a compile-time constant: `key >= S` is then false for every key tile but the last
 // (none at S = 32), so 12 of 13 tiles lose their per-score compare + select, and the 52 64-bit lane masks that spilled the
 // kernels' scalar registers into v_writelane / v_readlane pairs (SGPR spills 66 / 58 -> 0) disappear with them.
-#ifndef PVRL_ATTN_SFIX
-#define PVRL_ATTN_SFIX 1      // 0: A/B builds without the compile-time sequence lengths (tools/build_variant.py)
-#endif
 template <int NKT, int NW>
 int launch_fwd(const AttnArgs& p, hipStream_t s) {
   const dim3 grid((unsigned)(8 * ((p.nseq + 7) / 8) * p.H)), blk(64 * NW);
-  constexpr int SFIX = PVRL_ATTN_SFIX ? (NKT == 13 ? 197 : NKT == 2 ? 32 : 0) : 0;
+  constexpr int SFIX = NKT == 13 ? 197 : NKT == 2 ? 32 : 0;
   if (p.causal || p.kpm) hipLaunchKernelGGL((attn_fwd_kernel<NKT, true, NW>), grid, blk, 0, s, p);
   else if (SFIX && p.mp.S == SFIX) hipLaunchKernelGGL((attn_fwd_kernel<NKT, false, NW, SFIX>), grid, blk, 0, s, p);
   else hipLaunchKernelGGL((attn_fwd_kernel<NKT, false, NW>), grid, blk, 0, s, p);
@@ -518,7 +496,7 @@ int launch_fwd(const AttnArgs& p, hipStream_t s) {
 template <int NKT, int NW>
 int launch_bwd(const AttnArgs& p, hipStream_t s) {
   const dim3 grid((unsigned)(8 * ((p.nseq + 7) / 8) * p.H)), blk(64 * NW);
-  constexpr int SFIX = PVRL_ATTN_SFIX ? (NKT == 13 ? 197 : NKT == 2 ? 32 : 0) : 0;
+  constexpr int SFIX = NKT == 13 ? 197 : NKT == 2 ? 32 : 0;
   if (p.causal || p.kpm) {
     hipLaunchKernelGGL((attn_bwd_q_kernel<NKT, true, NW>), grid, blk, 0, s, p);
     PVRL_LAUNCH_CHECK();
@@ -576,7 +554,7 @@ extern "C" int pvrl_attn_bwd(const void* qkv, int64_t ld, int64_t nseq, int64_t 
   if (!o || !d_o || !lse || !dvec || !dqkv || (ldo % 8) || (ldd % 4)) return PVRL_EINVAL;
   if (mode == 1 && (!o_cls || !d_o_cls || !dqkv_cls)) return PVRL_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  if (attn_bwd_fused_enabled() && pvrl_attn_bwd_fused_ok(p)) return pvrl_attn_bwd_fused_launch(p, s);
+  if (pvrl_attn_bwd_fused_ok(p)) return pvrl_attn_bwd_fused_launch(p, s);
   if (pvrl_attn_bwd_s32_ok(p)) return pvrl_attn_bwd_s32_launch(p, s);
   if (S <= 16) return launch_bwd<1, 4>(p, s);
   if (S <= 32) return launch_bwd<2, 4>(p, s);

@@ -47,31 +47,19 @@ struct PA {
 // dK / dV kernel -- and the hardware deals consecutive workgroup ids round-robin over the 8 XCDs: with the natural (tile fastest) order
 // every XCD's L2 fetched every (b, h)'s shared operand (forward: 280 MB read per launch against 58 MB of operands; dK / dV: 995 MB at
 // 5.7 TB/s -- fabric-bound on re-reads).  1-D grid, id = 8 j + xcd: XCD x runs the (b, h) with bh % 8 == x, their tiles back to back.
-#ifndef PVRL_PATTN_XCD
-#define PVRL_PATTN_XCD 1
-#endif
 struct PBlk { int x, y, z; };
 __device__ __forceinline__ bool pattn_block(const PA& p, PBlk& o) {
   const int inner = p.gx * p.gz;
-#if PVRL_PATTN_XCD
   const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
   const int i = j % inner;
   o.y = (j / inner) * 8 + xcd;
-#else
-  const int i = blockIdx.x % inner;
-  o.y = blockIdx.x / inner;
-#endif
   o.x = i % p.gx;
   o.z = i / p.gx;
   return o.y < p.gy;
 }
 static unsigned pattn_grid(PA& p, long gx, long gy, long gz) {
   p.gx = (int)gx; p.gy = (int)gy; p.gz = (int)gz;
-#if PVRL_PATTN_XCD
   return (unsigned)(8 * ((gy + 7) / 8) * gx * gz);
-#else
-  return (unsigned)(gx * gy * gz);
-#endif
 }
 
 // Staging of a PAIR of 32 x 96 tiles (K | V, or Q | dO): 768 chunks of 16 B, exactly three per thread, no branches.  Chunk

@@ -20,13 +20,8 @@ constexpr int TILE = 8 * PITCH;
 // eight conversions pairs + eight FMAs: round 3 found both kernels VALU-bound, not HBM-bound (backward: 821 VALU instructions per
 // 7 KB item = 8.5 B/clk/CU = the 4.6 TB/s it ran at)
 __device__ __forceinline__ float dot8(const opx8 a, const opx8 b, float s = 0.f) {
-#if defined(PVRL_T8_NO_DOT2)        // A/B builds only (tools/build_variant.py)
-#pragma unroll
-  for (int e = 0; e < 8; ++e) s = fmaf((float)a[e], (float)b[e], s);
-#else
 #pragma unroll
   for (int e = 0; e < 4; ++e) s = FDOT2_F32((opx2){a[2 * e], a[2 * e + 1]}, (opx2){b[2 * e], b[2 * e + 1]}, s, false);
-#endif
   return s;
 }
 __device__ __forceinline__ opx8 lds8(const char* p) { return *reinterpret_cast<const opx8*>(p); }

@@ -108,34 +108,11 @@ __device__ __forceinline__ float wave_max(float v) {
 // v_fma_f32 in 4.3, v_pk_fma_f32 in 5 (two elements); the GELU GEMM 313 -> 305 us, the dGELU GEMM and the step unchanged within noise (the
 // epilogues are bound by their store traffic, the math runs under it).  Beyond |u| = 6 both saturate (gelu -> u or -6e-9, gelu' -> 1 or 0); a NaN goes
 // through the select and comes out as NaN.
-#ifndef PVRL_GELU_FORM
-#define PVRL_GELU_FORM 1      // 0: the Abramowitz-Stegun form (A/B builds, tools/build_variant.py)
-#endif
-#ifndef PVRL_DGELU_FORM
-#define PVRL_DGELU_FORM PVRL_GELU_FORM
-#endif
 __device__ __forceinline__ float gelu_clamp6(float u) {
   const float a = fabsf(u);
   return a > 6.0f ? 6.0f : a;       // (not fminf: v_min_f32 drops a NaN)
 }
-// erf via Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7 absolute): v_rcp_f32 (1 ulp, not the 10-instruction IEEE division), v_exp
-// and five FMAs; `e` returns exp(-x^2) for reuse by the derivative.  Kept for A/B builds (PVRL_GELU_FORM=0).
-__device__ __forceinline__ float erf_as(float x, float& e) {
-  const float ax = fabsf(x);
-  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.0f));
-  e = __expf(-ax * ax);
-  float p = fmaf(1.061405429f, t, -1.453152027f);
-  p = fmaf(p, t, 1.421413741f);
-  p = fmaf(p, t, -0.284496736f);
-  p = fmaf(p, t, 0.254829592f);
-  const float r = 1.0f - p * t * e;
-  return copysignf(r, x);
-}
 __device__ __forceinline__ float gelu_erf(float u) {
-#if PVRL_GELU_FORM == 0
-  float e;
-  return 0.5f * u * (1.0f + erf_as(u * 0.70710678118654752440f, e));
-#else
   const float x = gelu_clamp6(u);
   float p = fmaf(-2.9932052711956203e-05f, x, 0.0007281892467290163f);
   p = fmaf(p, x, -0.007909782230854034f);
@@ -145,15 +122,11 @@ __device__ __forceinline__ float gelu_erf(float u) {
   p = fmaf(p, x, 1.0f);
   const float h = __builtin_amdgcn_exp2f(-p);
   return fmaf(-x, h, fmaxf(u, 0.0f));
-#endif
 }
 // two elements at a time: packed-fp32 FMAs (v_pk_fma_f32, two lanes' worth per issue slot) -- written out because under the GELU
 // GEMM's register pressure the compiler otherwise falls back to one v_fmaak_f32 per element and coefficient
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2_t gelu_erf2(f32x2_t u) {
-#if PVRL_GELU_FORM == 0
-  return (f32x2_t){gelu_erf(u[0]), gelu_erf(u[1])};
-#else
   const f32x2_t x = {gelu_clamp6(u[0]), gelu_clamp6(u[1])};
   f32x2_t p = __builtin_elementwise_fma((f32x2_t)(-2.9932052711956203e-05f), x, (f32x2_t)(0.0007281892467290163f));
   p = __builtin_elementwise_fma(p, x, (f32x2_t)(-0.007909782230854034f));
@@ -164,14 +137,8 @@ __device__ __forceinline__ f32x2_t gelu_erf2(f32x2_t u) {
   const f32x2_t h = {__builtin_amdgcn_exp2f(-p[0]), __builtin_amdgcn_exp2f(-p[1])};
   const f32x2_t r = {fmaxf(u[0], 0.0f), fmaxf(u[1], 0.0f)};
   return __builtin_elementwise_fma(-x, h, r);
-#endif
 }
 __device__ __forceinline__ float gelu_erf_grad(float u) {
-#if PVRL_DGELU_FORM == 0
-  float e;  // = exp(-u^2 / 2)
-  const float cdf = 0.5f * (1.0f + erf_as(u * 0.70710678118654752440f, e));
-  return fmaf(u * 0.39894228040143267794f, e, cdf);
-#else
   const float x = gelu_clamp6(u);
   const float e = __builtin_amdgcn_exp2f(x * x * -0.72134752044448170368f);
   float n = fmaf(1.678248281677952e-06f, x, -3.60403792001307e-05f);
@@ -185,7 +152,6 @@ __device__ __forceinline__ float gelu_erf_grad(float u) {
   n = fmaf(n, x, -0.7978806495666504f);
   n = fmaf(n, x, 0.5f);
   return 0.5f + copysignf(0.5f - e * n, u);
-#endif
 }
 __device__ __forceinline__ float quick_gelu(float u) {
   return u * __builtin_amdgcn_rcpf(1.0f + __expf(-1.702f * u));
@@ -208,8 +174,8 @@ static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // CUs per XCD that the PERSISTENT / one-round kernels of this library size their grids for (gemm_nt8, gemm_tn8 and its grouped
 // launch, attn_bwd_fused: one 512-thread workgroup owns a whole CU -- 256 VGPRs per lane, 128 KB of LDS).  Default: all of them
-// (MI355X: 256 CUs / 8 XCDs = 32).  PVRL_COMPUTE_CUS=<n> (read once per process, like the PVRL_NT* A/B switches: the one piece
-// of process-wide launch configuration in the library) leaves 32 - n CUs per XCD to kernels of OTHER streams: in a data-parallel job
+// (MI355X: 256 CUs / 8 XCDs = 32).  PVRL_COMPUTE_CUS=<n> (read once per process: the one piece of process-wide
+// launch configuration in the library) leaves 32 - n CUs per XCD to kernels of OTHER streams: in a data-parallel job
 // RCCL's channel kernels take CUs at a kernel seam and then hold them for the length of a collective; a persistent grid sized for
 // CUs it cannot get pays a second wave of workgroups -- up to 2x on that launch (distributed.reserve_comm_cus sets both this and
 // RCCL's channel count before the first launch; measured cost of the reservation on one GPU: DESIGN.md section 6).

@@ -1,6 +1,5 @@
 // bf16 MFMA GEMM, "NT" form: the C-ABI entry points.  The kernel, its epilogues and the tile launcher live in
 // gemm_nt_core.h (shared with the measured-and-rejected variants kept under tools/probe/, which are NOT part of this library).
-#include <cstdlib>
 #include "gemm_nt_core.h"
 #include "gemm_nt8_core.h"
 #include "gemm_nt_skinny.h"
@@ -112,6 +111,9 @@ static int f32_small_plan(int64_t M, int64_t N, int64_t K, int* kchunk_out) {
   return cdiv(K, kchunk);
 }
 
+// rows from which the mid-sized shapes take 256 x 128 tiles instead of 128 x 128
+constexpr int NT_MID_M = 2048;
+
 // Tile selection: 256x256 / 16 waves for the encoder's 50k-row GEMMs (M >= 4096 and N a multiple of 256), 256x128 for
 // mid-sized M, 128x128 / 4 waves (two workgroups per CU) for the small-M stacks (order transformer, CLIP text) and for
 // every N that is not a multiple of 256 (MViT's 128 / 384 / 640 / 1152-wide layers: 128x128 measured 5-16 % ahead of
@@ -119,105 +121,25 @@ static int f32_small_plan(int64_t M, int64_t N, int64_t K, int* kchunk_out) {
 // epilogue is the exception).
 // (Cutting the ragged last wave of 256x256 tiles off into a 128x128-tile launch was measured 12 % SLOWER: the second
 //  launch serialises behind the first; one launch with a partly idle last wave wins.)
-// CUs per XCD of the current device (MI355X: 256 / 8 = 32) -- sizes the last-round split (gemm_nt_core.h nt_tail_plan)
-int nt_cus_per_xcd() {
-  static int cus = 0;
-  if (cus == 0) {
-    cus = pvrl_compute_cus_per_xcd();           // (common.h: all CUs of an XCD, or PVRL_COMPUTE_CUS of them)
-    const char* e = getenv("PVRL_NT_CUS");      // probe runs: fewer persistent workgroups per XCD for this kernel family only
-    if (e && atoi(e) > 0 && atoi(e) < cus) cus = atoi(e);
-  }
-  return cus;
-}
-#ifndef PVRL_NT_TAILS_DEFAULT
-#define PVRL_NT_TAILS_DEFAULT 1
-#endif
-// PVRL_NT_TAILS=0 switches the sub-tiling of the ragged last round off (A/B runs; read once)
-int nt_tails_enabled() {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("PVRL_NT_TAILS");
-    on = e ? (e[0] == '0' ? 0 : 1) : PVRL_NT_TAILS_DEFAULT;
-  }
-  return on;
-}
-
-int nt_wide_enabled() {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("PVRL_NT_WIDE");
-    on = e ? (e[0] == '0' ? 0 : 1) : 1;
-  }
-  return on;
-}
-
-// PVRL_NT8=0 sends the 256x256 shapes back to the 16-wave one-tile kernel (A/B runs, tools/bench_kernels.py); read once
-int nt8_enabled() {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("PVRL_NT8");
-    on = e ? (e[0] == '0' ? 0 : 1) : 1;
-  }
-  return on;
-}
-
-// rows from which the mid-sized shapes take 256 x 128 tiles instead of 128 x 128 (PVRL_NT_MID_M: A/B runs; read once)
-int nt_mid_m() {
-  static int m = -1;
-  if (m < 0) {
-    const char* e = getenv("PVRL_NT_MID_M");
-    m = e && atoi(e) > 0 ? atoi(e) : 2048;
-  }
-  return m;
-}
-
-// PVRL_NT_TILE=22|42|44|26|25 forces a tile shape where it is legal for the problem (shape sweeps: tools/probe/mvit_gemm_times.py); read once
-int nt_forced_tile() {
-  static int t = -1;
-  if (t < 0) {
-    const char* e = getenv("PVRL_NT_TILE");
-    t = e ? atoi(e) : 0;
-  }
-  return t;
-}
-
-// PVRL_NT_SKINNY=0 sends the few-row problems (M <= 192: the pre-training head's stack) back to the 128 x 128 tile (A/B runs; read once)
-int nt_skinny_enabled() {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("PVRL_NT_SKINNY");
-    on = e ? (e[0] == '0' ? 0 : 1) : 1;
-  }
-  return on;
-}
-
 template <int EPI>
 int launch_nt(const GemmNT& p, hipStream_t s) {
   constexpr bool two_out = EPI == PVRL_EPI_GELU || EPI == PVRL_EPI_QGELU;
-  if (nt_skinny_ok(p) && nt_forced_tile() == 0 && nt_skinny_enabled()) return launch_nt_skinny<EPI>(p, s);
-  switch (nt_forced_tile()) {
-    case 22: return launch_tile<EPI, 2, 2>(p, s);
-    case 42: return launch_tile<EPI, 4, 2>(p, s);
-    case 44: if (p.N % 256 == 0) return launch_tile<EPI, 4, 4>(p, s); break;
-    case 26: if (p.N % 384 == 0) return launch_tile<EPI, 2, 6>(p, s); break;
-    case 25: if (p.N % 320 == 0) return launch_tile<EPI, 2, 5>(p, s); break;
-    default: break;
-  }
-  if (nt_wide_enabled() && p.N == 768 && p.M >= 4096 && p.M < 20000) return launch_tile<EPI, 2, 6>(p, s);   // MViT stage 4 (M = 12,576): 99 tiles of 128 x 384 x 2 fill 198 CUs; 256 x 256 tiles 150 (-10 %)
+  if (nt_skinny_ok(p)) return launch_nt_skinny<EPI>(p, s);
+  if (p.N == 768 && p.M >= 4096 && p.M < 20000) return launch_tile<EPI, 2, 6>(p, s);   // MViT stage 4 (M = 12,576): 99 tiles of 128 x 384 x 2 fill 198 CUs; 256 x 256 tiles 150 (-10 %)
   if (p.M >= 4096 && p.N % 256 == 0) {
     // persistent 8-wave ping-pong kernel (gemm_nt8_core.h); its load stream runs two K-tiles ahead, so K >= 128
     // (the fp32-table form of PVRL_EPI_RESID_16 -- the embedding prologue, one launch per step -- lives in the one-tile kernel only)
-    if (nt8_enabled() && p.K >= 2 * BK && !(EPI == PVRL_EPI_RESID_16 && p.aux_rowmod != 0)) return launch_nt8<EPI>(p, s);
+    if (p.K >= 2 * BK && !(EPI == PVRL_EPI_RESID_16 && p.aux_rowmod != 0)) return launch_nt8<EPI>(p, s);
     return launch_tile<EPI, 4, 4>(p, s);
   }
   // N = 384 / 1152 and 640 at M >= 100k rows (MViTv2-S stages 1-2): one 128 x 384 / 128 x 320 tile row instead of three / five 128 x 128
   // column tiles -- the A panel is fetched once and a workgroup's fixed costs cover 3x / 2.5x the output (8-23 % per shape; at
-  // M = 50,208 the 128 x 128 tiles' two workgroups per CU win by 5-9 %: gpurun_out/r3_w_shapes_*.txt).  PVRL_NT_WIDE=0: A/B runs
-  if (nt_wide_enabled() && p.M >= 4096 && p.N % 256 != 0) {
+  // M = 50,208 the 128 x 128 tiles' two workgroups per CU win by 5-9 %)
+  if (p.M >= 4096 && p.N % 256 != 0) {
     if (p.N % 384 == 0 && p.M >= 100000) return launch_tile<EPI, 2, 6>(p, s);
     if (p.N % 320 == 0) return launch_tile<EPI, 2, 5>(p, s);
   }
-  if (p.M >= nt_mid_m() && (p.N % 256 == 0 || two_out)) return launch_tile<EPI, 4, 2>(p, s);
+  if (p.M >= NT_MID_M && (p.N % 256 == 0 || two_out)) return launch_tile<EPI, 4, 2>(p, s);
   return launch_tile<EPI, 2, 2>(p, s);
 }
 
@@ -240,7 +162,7 @@ extern "C" int pvrl_gemm_nt_bf16(const void* A, int64_t lda, const void* W, int6
   p.M = (int)M; p.N = (int)N; p.K = (int)K;
   p.bias = bias; p.bias2 = bias2; p.rowscale = rowscale; p.aux = aux; p.aux_ld = aux_ld; p.aux_rowmod = (int)aux_rowmod;
   p.out0 = out0; p.ld0 = ld0; p.out1 = out1; p.ld1 = ld1; p.m_off = 0; p.gm = 0;      // 0: launch_tile picks the rasterisation group height for the shape
-  p.cus = nt_cus_per_xcd(); p.tails = nt_tails_enabled();
+  p.cus = pvrl_compute_cus_per_xcd(); p.tails = 1;
   hipStream_t s = (hipStream_t)stream;
   switch (epilogue) {
     case PVRL_EPI_BF16: return launch_nt<PVRL_EPI_BF16>(p, s);
@@ -272,8 +194,8 @@ extern "C" int pvrl_gemm_nt_batched_bf16(int nprob, const pvrl_nt_problem* probl
       p.M = (int)q.M; p.N = (int)q.N; p.K = (int)q.K;
       p.bias = q.bias; p.bias2 = nullptr; p.rowscale = q.rowscale; p.aux = q.aux; p.aux_ld = q.aux_ld; p.aux_rowmod = 0;
       p.out0 = q.out0; p.ld0 = q.ld0; p.out1 = nullptr; p.ld1 = 0; p.m_off = 0;
-      p.cus = nt_cus_per_xcd(); p.tails = 0;
-      p.tiles_n = p.N / 128; p.tiles_m = cdiv(p.M, 128); p.gm = nt_gm_for(p.tiles_n);
+      p.cus = pvrl_compute_cus_per_xcd(); p.tails = 0;
+      p.tiles_n = p.N / 128; p.tiles_m = cdiv(p.M, 128); p.gm = NT_GM;
       p.nwg = 8 * cdiv(p.tiles_m, 8) * p.tiles_n;
       g.first[i] = blocks;
       blocks += p.nwg;
@@ -289,16 +211,6 @@ extern "C" int pvrl_gemm_nt_batched_bf16(int nprob, const pvrl_nt_problem* probl
   return PVRL_OK;
 }
 
-// PVRL_F32_SMALL_MFMA=0 keeps every shape on the 64 x 64-tile FMA kernel (A/B runs; read once)
-static int f32_small_mfma_enabled() {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("PVRL_F32_SMALL_MFMA");
-    on = e ? (e[0] == '0' ? 0 : 1) : 1;
-  }
-  return on;
-}
-
 extern "C" int64_t pvrl_gemm_nt_f32_small_workspace_bytes(int64_t M, int64_t N, int64_t K) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
   const int splits = f32_small_plan(M, N, K, nullptr);
@@ -310,10 +222,8 @@ extern "C" int pvrl_gemm_nt_f32_small(const float* A, int64_t lda, const float* 
                                       void* workspace, int64_t workspace_bytes, void* stream) {
   if (M <= 0 || N <= 0) return PVRL_OK;
   if (!A || !B || !C || K <= 0) return PVRL_EINVAL;
-  if (f32_small_mfma_enabled()) {       // K % 128 == 0: one workgroup per 16 columns of B, fp32 MFMA (cls_chain.hip)
-    int st = PVRL_OK;
-    if (pvrl_cls_gemm_f32(A, lda, B, ldb, bias, alpha, C, ldc, M, N, K, (hipStream_t)stream, &st)) return st;
-  }
+  int st = PVRL_OK;       // K % 128 == 0: one workgroup per 16 columns of B, fp32 MFMA (cls_chain.hip)
+  if (pvrl_cls_gemm_f32(A, lda, B, ldb, bias, alpha, C, ldc, M, N, K, (hipStream_t)stream, &st)) return st;
   int kchunk;
   const int splits = f32_small_plan(M, N, K, &kchunk);
   if (splits > 1 && (!workspace || workspace_bytes < pvrl_gemm_nt_f32_small_workspace_bytes(M, N, K))) return PVRL_EINVAL;

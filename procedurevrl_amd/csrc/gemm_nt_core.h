@@ -48,11 +48,7 @@ constexpr int BK = 64;
 // of 2 / 3 / 4 / 6 / 8): gm 2 +0.3 %, 3 +-0, 5 +0.9 %, 6 +0.8 ... +1.0 % (twice), 8 +0.3 %, 12 +0.4 % -> 6 for every shape (with three or
 // fewer tile columns the group height does not change what runs together).  The gain is in the L2, not in HBM bytes: FETCH_SIZE per
 // launch went UP 8-15 % on the wide shapes (profiles/r4_pmc_hbm_mfma.csv) while the kernels got 1-3 % shorter.
-#ifndef PVRL_NT_GM
-#define PVRL_NT_GM 0
-#endif
-constexpr int NT_GM = PVRL_NT_GM;       // 0 = the default below, otherwise forced (probe builds)
-static inline int nt_gm_for(int tiles_n) { (void)tiles_n; return NT_GM ? NT_GM : 6; }
+constexpr int NT_GM = 6;
 
 __device__ __forceinline__ int swz_x(int row) { return (row >> 1) & 7; }
 // W rows are read in a permuted order so that the lanes of one epilogue store instruction write contiguous bytes:
@@ -68,18 +64,11 @@ template <bool F32OUT> __device__ __forceinline__ int swz_w(int row) {
   return ((row >> 1) & 1) | (((row >> 3) & 3) << 1);
 }
 
-// ---- cache policy of the epilogue's memory traffic (gfx950 `aux` bits of the raw buffer instructions: 1 = sc0, 2 = nt,
-// 16 = sc1).  An epilogue GEMM streams hundreds of MB exactly once -- the fp32 residual / stored pre-activation in, the
-// outputs out (consumed by a LATER kernel) -- through a 4 MiB XCD L2 that should be holding the W tiles and A panels the
-// main loop re-reads: with default-policy stores every output line is kept in L2 and evicts them (round 2: the GELU GEMM
-// fetched 480 MB per launch against 82 MB of operands).  `sc1` stores are written through and dropped (MI355X guide,
-// "stores of each flavour"); `nt` marks the read-once loads as streaming.  Swept on MI355X: profiles/r3_nt_cache_policy.txt.
-#ifndef PVRL_NT_ST_AUX
-#define PVRL_NT_ST_AUX 0
-#endif
-#ifndef PVRL_NT_LD_AUX
-#define PVRL_NT_LD_AUX 0
-#endif
+// ---- cache policy of the epilogue's memory traffic: the default.  An epilogue GEMM streams hundreds of MB exactly once -- the
+// fp32 residual / stored pre-activation in, the outputs out (consumed by a LATER kernel) -- through a 4 MiB XCD L2 that should be
+// holding the W tiles and A panels the main loop re-reads, but written-through `sc1` stores and streaming `nt` loads (gfx950
+// `aux` bits of the raw buffer instructions) were swept on MI355X and every combination was slower than the default policy
+// (profiles/r3_nt_cache_policy.txt).
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
 // descriptor over `rows` rows of a row-major matrix starting at `base` (all arguments wave-uniform: kernel arguments and
 // blockIdx-derived tile origins).  Offsets past the last row are dropped (stores) / read as zero (loads) by the hardware
@@ -87,22 +76,14 @@ typedef __amdgpu_buffer_rsrc_t rsrc_t;
 __device__ __forceinline__ rsrc_t tile_rsrc(const void* base, long row0, long ld, int elem, int rows) {
   return __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)base + row0 * ld * elem), 0, (int)(rows * ld * elem), 0x00020000);
 }
-// Probe builds only (tools/probe/nt8_ab.py epi; results are garbage): bit 0 = the epilogue's stores are dropped (values kept alive),
-// bit 1 = the activation math is replaced by the identity, bit 2 = the epilogue's loads (residual / pre-activation) are dropped
-#ifndef PVRL_NT_EPI_ABLATE
-#define PVRL_NT_EPI_ABLATE 0
-#endif
-template <int AUX> __device__ __forceinline__ void bst16(rsrc_t r, unsigned off, f32x4 v) {
-  if (PVRL_NT_EPI_ABLATE & 1) { asm volatile("" :: "v"(v), "v"(off)); return; }
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, off, 0, AUX);
+__device__ __forceinline__ void bst16(rsrc_t r, unsigned off, f32x4 v) {
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, off, 0, 0);
 }
-template <int AUX> __device__ __forceinline__ void bst16(rsrc_t r, unsigned off, opx8 v) {
-  if (PVRL_NT_EPI_ABLATE & 1) { asm volatile("" :: "v"(v), "v"(off)); return; }
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, off, 0, AUX);
+__device__ __forceinline__ void bst16(rsrc_t r, unsigned off, opx8 v) {
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, off, 0, 0);
 }
-template <int AUX, typename T> __device__ __forceinline__ T bld16(rsrc_t r, unsigned off) {
-  if (PVRL_NT_EPI_ABLATE & 4) { u32x4 z = {off, 0x3c003c00u, 0x3c003c00u, off}; asm volatile("" : "+v"(z)); return __builtin_bit_cast(T, z); }
-  return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, AUX));
+template <typename T> __device__ __forceinline__ T bld16(rsrc_t r, unsigned off) {
+  return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
 }
 
 // The epilogue of ONE 64-row x 64-column accumulator block acc[mt][nt] (4 x 4 MFMA tiles of 16 x 16, operands swapped: a lane owns
@@ -117,7 +98,6 @@ template <int AUX, typename T> __device__ __forceinline__ T bld16(rsrc_t r, unsi
 template <int EPI, int BATCH = 2, bool TAB = false>
 __device__ __forceinline__ void nt_epilogue_at(const GemmNT& p, f32x4 (&acc)[4][4], int m0, int n0, int rb, int c0, int c1, int lane) {
   constexpr bool F32OUT = (EPI == PVRL_EPI_RESID_F32 || EPI == PVRL_EPI_F32);
-  constexpr int ST = PVRL_NT_ST_AUX, LD = PVRL_NT_LD_AUX;
   static_assert(BATCH == 1 || BATCH == 2 || BATCH == 4, "row tiles per load batch");
   const int q = lane >> 4, i = lane & 15;
   const int ncol[2] = {n0 + c0 + 8 * q, n0 + c1 + 8 * q};   // this lane's first column of each 32-column group
@@ -170,7 +150,7 @@ __device__ __forceinline__ void nt_epilogue_at(const GemmNT& p, f32x4 (&acc)[4][
 #pragma unroll
           for (int nt = 0; nt < 4; ++nt) {
             const unsigned off = ab + (unsigned)(ncol[nt >> 1] + 4 * (nt & 1)) * 4u;
-            rv[h][nt] = tab ? bld16<0, f32x4>(ra, off) : bld16<LD, f32x4>(ra, off);
+            rv[h][nt] = bld16<f32x4>(ra, off);
           }
         }
       }
@@ -191,7 +171,7 @@ __device__ __forceinline__ void nt_epilogue_at(const GemmNT& p, f32x4 (&acc)[4][
               for (int e = 0; e < 4; ++e) ov[e] += __shfl(b2lane, 32 * (nt >> 1) + 8 * q + 4 * (nt & 1) + e, 64);
             }
           }
-          bst16<ST>(ro, ob + (unsigned)(ncol[nt >> 1] + 4 * (nt & 1)) * 4u, ov);   // rows past M: dropped by the bounds check
+          bst16(ro, ob + (unsigned)(ncol[nt >> 1] + 4 * (nt & 1)) * 4u, ov);   // rows past M: dropped by the bounds check
         }
       }
     }
@@ -237,7 +217,7 @@ __device__ __forceinline__ void nt_epilogue_at(const GemmNT& p, f32x4 (&acc)[4][
         for (int h = 0; h < BATCH; ++h) {
           const unsigned ab = (unsigned)(rb + (BATCH * bt + h) * 16 + i) * (unsigned)p.aux_ld * 2u;
 #pragma unroll
-          for (int c = 0; c < 2; ++c) uv[h][c] = bld16<LD, opx8>(ra, ab + (unsigned)ncol[c] * 2u);
+          for (int c = 0; c < 2; ++c) uv[h][c] = bld16<opx8>(ra, ab + (unsigned)ncol[c] * 2u);
         }
       }
 #pragma unroll
@@ -258,7 +238,7 @@ __device__ __forceinline__ void nt_epilogue_at(const GemmNT& p, f32x4 (&acc)[4][
             opx8 o0;
 #pragma unroll
             for (int e = 0; e < 8; ++e) o0[e] = (op_t)(rs * v[e]);
-            bst16<ST>(r0, o0off, o0);
+            bst16(r0, o0off, o0);
           } else if constexpr (TWO) {
             opx8 u0, g0;
 #pragma unroll
@@ -266,7 +246,7 @@ __device__ __forceinline__ void nt_epilogue_at(const GemmNT& p, f32x4 (&acc)[4][
               u0[e] = (op_t)v[e];
               u0[e + 1] = (op_t)v[e + 1];
               if constexpr (EPI == PVRL_EPI_GELU) {
-                const f32x2_t gg = (PVRL_NT_EPI_ABLATE & 2) ? (f32x2_t){v[e] + 1.f, v[e + 1] + 1.f} : gelu_erf2((f32x2_t){v[e], v[e + 1]});
+                const f32x2_t gg = gelu_erf2((f32x2_t){v[e], v[e + 1]});
                 g0[e] = (op_t)gg[0];
                 g0[e + 1] = (op_t)gg[1];
               } else {
@@ -274,14 +254,14 @@ __device__ __forceinline__ void nt_epilogue_at(const GemmNT& p, f32x4 (&acc)[4][
                 g0[e + 1] = (op_t)quick_gelu(v[e + 1]);
               }
             }
-            bst16<ST>(r0, o0off, u0);
-            bst16<ST>(r1, ml * (unsigned)p.ld1 * 2u + (unsigned)ncol[c] * 2u, g0);
+            bst16(r0, o0off, u0);
+            bst16(r1, ml * (unsigned)p.ld1 * 2u + (unsigned)ncol[c] * 2u, g0);
           } else if constexpr (RES16) {
             float a[8];
             if constexpr (tab) {
               const int mr = (min(m0 + (int)ml, p.M - 1) + p.m_off) % p.aux_rowmod;
               const unsigned ab = (unsigned)mr * (unsigned)p.aux_ld * 4u + (unsigned)ncol[c] * 4u;
-              const f32x4 t0 = bld16<0, f32x4>(ra, ab), t1 = bld16<0, f32x4>(ra, ab + 16u);
+              const f32x4 t0 = bld16<f32x4>(ra, ab), t1 = bld16<f32x4>(ra, ab + 16u);
 #pragma unroll
               for (int e = 0; e < 4; ++e) { a[e] = t0[e]; a[4 + e] = t1[e]; }
             } else {
@@ -296,16 +276,16 @@ __device__ __forceinline__ void nt_epilogue_at(const GemmNT& p, f32x4 (&acc)[4][
             opx8 o0;
 #pragma unroll
             for (int e = 0; e < 8; ++e) o0[e] = (op_t)(rs * v[e] + a[e]);
-            bst16<ST>(r0, o0off, o0);
+            bst16(r0, o0off, o0);
           } else {  // PVRL_EPI_DGELU / PVRL_EPI_DQGELU : out = rs * acc * act'(u)
             const opx8 ua = uv[h][c];
             opx8 o0;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-              const float d = (PVRL_NT_EPI_ABLATE & 2) ? (float)ua[e] : EPI == PVRL_EPI_DGELU ? gelu_erf_grad((float)ua[e]) : quick_gelu_grad((float)ua[e]);
+              const float d = EPI == PVRL_EPI_DGELU ? gelu_erf_grad((float)ua[e]) : quick_gelu_grad((float)ua[e]);
               o0[e] = (op_t)(rs * v[e] * d);
             }
-            bst16<ST>(r0, o0off, o0);
+            bst16(r0, o0off, o0);
           }
         }
       }
@@ -562,7 +542,7 @@ template <int EPI, int WM, int WN>
 int launch_tile(GemmNT p, hipStream_t s) {
   p.tiles_n = p.N / (64 * WN);
   p.tiles_m = cdiv(p.M, 64 * WM);
-  if (p.gm <= 0) p.gm = nt_gm_for(p.tiles_n);
+  if (p.gm <= 0) p.gm = NT_GM;
   p.nwg = 8 * cdiv(p.tiles_m, 8) * p.tiles_n;   // per-XCD tile lists padded to equal length (surplus blocks exit)
   if (WM == 4 && WN == 4) {                     // XCDs own ceil or floor(tiles_m / 8) panels: the longer block list sizes the grid
     const int qm = p.tiles_m >> 3, rm = p.tiles_m & 7;

@@ -1,6 +1,5 @@
 // bf16 MFMA GEMM, "TN" form (weight gradients): the C-ABI entry points.  The kernels live in gemm_tn_core.h.
 #include <algorithm>
-#include <cstdlib>
 #include "gemm_tn8_core.h"
 
 namespace {
@@ -10,18 +9,10 @@ namespace {
 // transposing-read kernel.  (Measured-and-rejected alternatives live under tools/probe/, outside this library.)
 bool tn_use_rt(int64_t N, int64_t K) { return (N % 128 == 0) && (K % 128 == 0) && N * K >= 256 * 256; }
 // The ping-pong LDS-DMA kernel (gemm_tn8_core.h) takes the shapes made of whole 256x256 tiles -- every Linear of the ViT-B encoder;
-// PVRL_TN8=0 sends them back to the register-transposed kernel (A/B runs; read once).  Results are bit-identical either way.
-bool tn8_enabled() {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("PVRL_TN8");
-    on = e ? (e[0] == '0' ? 0 : 1) : 1;
-  }
-  return on != 0;
-}
+// its results are bit-identical to the register-transposed kernel's.
 // (its buffer descriptors and per-lane offsets are 32-bit: a slice's rows x the row pitch must stay below 2 GiB)
 bool tn_use_tn8(int64_t N, int64_t K, int64_t slice_rows, int64_t ldp, int64_t ldq) {
-  return tn8_enabled() && (N % 256 == 0) && (K % 256 == 0) && (slice_rows + 64) * std::max(ldp, ldq) * 2 < (int64_t(1) << 31) - 4096;
+  return (N % 256 == 0) && (K % 256 == 0) && (slice_rows + 64) * std::max(ldp, ldq) * 2 < (int64_t(1) << 31) - 4096;
 }
 
 }  // namespace

@@ -34,16 +34,7 @@ constexpr int TN8_BUF = 4 * TN8_HALF;    // one stage: P0 P1 Q0 Q1
 #pragma clang diagnostic ignored "-Winline-asm"
 // one 1 KiB LDS-DMA copy through a buffer descriptor: lane l's 16 bytes at r.base + soff + voff land at LDS byte lds + 16 l; offsets
 // past the descriptor's size read as zero.  (s_nop 4: SGPRs written by v_readfirstlane -> vector-memory instruction; s_nop 0: M0.)
-// Probe builds only (tools/probe/tn_ab.py; results are garbage, only the time means something): bit 0 = no LDS-DMA, bit 1 = no fragment
-// reads, bit 2 = no MFMAs
-#ifndef PVRL_TN8_ABLATE
-#define PVRL_TN8_ABLATE 0
-#endif
-#ifndef PVRL_TN8_PH2
-#define PVRL_TN8_PH2 1      // 0: four phases of 16 MFMAs per K-tile (A/B builds)
-#endif
 __device__ __forceinline__ void tn8_dma16(tn_rsrc_t r, unsigned voff, unsigned soff, unsigned lds) {
-  if (PVRL_TN8_ABLATE & 1) return;
   asm volatile("s_nop 4\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds"
                :: "v"(voff), "s"(r), "s"(soff), "s"(lds) : "memory", "m0");
 }
@@ -128,34 +119,17 @@ __device__ __forceinline__ void tn8_pair(const GemmTN& p, const int pair, char* 
   opx8 ra[4][2], rb0[2][2], rb1[2][2];                     // [n tile][m half], [h2][m half] (rb0 / rb1: k half 0 / 1)
   f32x4 acc[2][4][4];                                      // [n half][n tile][2 c + h2]
   float cacc[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-  if (PVRL_TN8_ABLATE & 2) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) ra[t][ks] = (opx8)(op_t)0.5f;
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) { rb0[h][ks] = (opx8)(op_t)0.25f; rb1[h][ks] = (opx8)(op_t)0.125f; }
-  }
   opx2 ones2;
   ones2[0] = (op_t)1.0f; ones2[1] = (op_t)1.0f;
   auto rdP = [&](const char* buf, int mh, int ks) {        // 8 reads: the n half's 4 tiles of this wave, m half ks
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      if (PVRL_TN8_ABLATE & 2) asm volatile("" : "+v"(ra[t][ks]));
-      else ra[t][ks] = tr_frag(buf + mh * TN8_HALF + ks * 8192 + t * 128, xb, xb + 1024);
-    }
+    for (int t = 0; t < 4; ++t) ra[t][ks] = tr_frag(buf + mh * TN8_HALF + ks * 8192 + t * 128, xb, xb + 1024);
   };
   auto rdQ = [&](const char* buf, int ks) {                // 8 reads: both k halves, m half ks (kept for both n halves)
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      if (PVRL_TN8_ABLATE & 2) {
-        asm volatile("" : "+v"(rb0[h][ks]), "+v"(rb1[h][ks]));
-      } else {
-        rb0[h][ks] = tr_frag(buf + 2 * TN8_HALF + ks * 8192 + h * 128, wb, wb + 1024);
-        rb1[h][ks] = tr_frag(buf + 3 * TN8_HALF + ks * 8192 + h * 128, wb, wb + 1024);
-      }
+      rb0[h][ks] = tr_frag(buf + 2 * TN8_HALF + ks * 8192 + h * 128, wb, wb + 1024);
+      rb1[h][ks] = tr_frag(buf + 3 * TN8_HALF + ks * 8192 + h * 128, wb, wb + 1024);
     }
   };
   auto mmk = [&](f32x4 (&a)[4][4], int mh, int ks) {       // 16 MFMAs on 16 different accumulators
@@ -163,12 +137,8 @@ __device__ __forceinline__ void tn8_pair(const GemmTN& p, const int pair, char* 
     for (int t = 0; t < 4; ++t)
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        if (PVRL_TN8_ABLATE & 4) {
-          asm volatile("" :: "v"(rb0[h][ks]), "v"(rb1[h][ks]), "v"(ra[t][ks]));
-        } else {
-          a[t][h] = MFMA_16x16x32(rb0[h][ks], ra[t][ks], a[t][h], 0, 0, 0);
-          a[t][2 + h] = MFMA_16x16x32(rb1[h][ks], ra[t][ks], a[t][2 + h], 0, 0, 0);
-        }
+        a[t][h] = MFMA_16x16x32(rb0[h][ks], ra[t][ks], a[t][h], 0, 0, 0);
+        a[t][2 + h] = MFMA_16x16x32(rb1[h][ks], ra[t][ks], a[t][2 + h], 0, 0, 0);
       }
     if (do_csum) {                                         // column sums of P
 #pragma unroll
@@ -203,8 +173,7 @@ __device__ __forceinline__ void tn8_pair(const GemmTN& p, const int pair, char* 
     const unsigned lb = sbase + cur * TN8_BUF, lo = sbase + (cur ^ 1) * TN8_BUF;
     // every memory segment issues its fragment reads FIRST and the LDS-DMA behind them (a DMA instruction blocks its wave while the
     // CU's address path takes the 1 KiB; the reads complete underneath)
-#if PVRL_TN8_PH2
-    // TWO phases per stage (n half, both m halves: 32 MFMAs each): half the barriers of the four-phase form below, same copies and waits; ~1 % faster
+    // TWO phases per stage (n half, both m halves: 32 MFMAs each): half the barriers of a four-phase form, same copies and waits; ~1 % faster
     rdP(rbuf, 0, 0); rdQ(rbuf, 0); rdP(rbuf, 0, 1); rdQ(rbuf, 1);
     if (on1) {
       issueP1(1, 0, lo, sP1); issueP1(1, 1, lo, sP1);
@@ -228,44 +197,6 @@ __device__ __forceinline__ void tn8_pair(const GemmTN& p, const int pair, char* 
     mmk(acc[1], 1, 0);
     mmk(acc[1], 1, 1);
     TN8_CMP_END();
-#else
-    // ---- phase 0: n half 0, m half 0 ----
-    rdP(rbuf, 0, 0);
-    rdQ(rbuf, 0);
-    if (on1) issueP1(1, 0, lo, sP1);
-    TN8_MEM_END();
-    mmk(acc[0], 0, 0);
-    TN8_CMP_END();
-    // ---- phase 1: n half 0, m half 1; behind it this slot's P0 / Q0 / Q1 are free.  Waits for this stage's P1 (read in phase 2) ----
-    rdP(rbuf, 0, 1);
-    rdQ(rbuf, 1);
-    if (on1) {
-      issueP1(1, 1, lo, sP1);
-      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");     // younger than this stage's P1: 3 + 3 of the previous stage, 1 + 1 of this one
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    TN8_MEM_END();
-    mmk(acc[0], 0, 1);
-    TN8_CMP_END();
-    // ---- phase 2: n half 1, m half 0 ----
-    rdP(rbuf, 1, 0);
-    if (on2) { issueQ1(0, 0, lb, sQ2); issueQ1(0, 1, lb, sQ2); issueP1(0, 0, lb, sP2); }
-    TN8_MEM_END();
-    mmk(acc[1], 1, 0);
-    TN8_CMP_END();
-    // ---- phase 3: n half 1, m half 1; behind it this slot's P1 is free.  Waits for the next stage's P0 / Q0 / Q1 ----
-    rdP(rbuf, 1, 1);
-    if (on2) {
-      issueP1(0, 1, lb, sP2); issueQ1(1, 0, lb, sQ2); issueQ1(1, 1, lb, sQ2);
-      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");     // younger than the next stage's P0 / Q0 / Q1: 1 + 1 + 3 + 3 of this stage
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    TN8_MEM_END();
-    mmk(acc[1], 1, 1);
-    TN8_CMP_END();
-  #endif
   }
   if (wm == 0) TN8_BARRIER();                              // both groups leave the loop together
 

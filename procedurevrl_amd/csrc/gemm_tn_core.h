@@ -241,14 +241,11 @@ __device__ __forceinline__ void tn_rt8_pair(const GemmTN& p, const int pair, cha
   // -> block map is chosen so that those waves are 4..7, ONE PER SIMD (waves w and w + 4 share a SIMD): the other wave of each
   // SIMD then has the matrix pipe to itself.
   const bool nfull = n0 + 256 <= p.N, kfull = k0 + 256 <= p.K;
-#ifndef PVRL_TN_SKIP_PAD
-#define PVRL_TN_SKIP_PAD 1                                 // 0: A/B builds (tools/build_variant.py) -- MFMAs over the zero half as before
-#endif
-  const bool remap = PVRL_TN_SKIP_PAD && !nfull;
+  const bool remap = !nfull;
   const int wn = remap ? (wave >> 2) : (wave & 1);         // 2 x 4 waves: 128 n x 64 k each
   const int wk = remap ? (wave & 3) : (wave >> 1);
   const bool n_ok = nfull || wn == 0, k_ok = kfull || wk < 2;
-  const bool compute = !PVRL_TN_SKIP_PAD || (n_ok && k_ok);   // wave-uniform
+  const bool compute = n_ok && k_ok;   // wave-uniform
   const int mbeg = s * p.Ms;
   const int mend = min(p.M, mbeg + p.Ms);
   const int rows = mend - mbeg;
@@ -280,13 +277,7 @@ __device__ __forceinline__ void tn_rt8_pair(const GemmTN& p, const int pair, cha
   // Round 3: a half tile's stages used to take the masked path below for EVERY stage -- plain loads whose values the mask consumes
   // at once, i.e. an s_waitcnt vmcnt(0) inside gload and the load latency exposed once per stage (2.45 us per stage at N = 128
   // against 1.9 for full tiles).  They now take the asm loads like everyone else; the mask is applied when the set is waited for.
-  // Probe builds only (tools/probe/tn_ab.py; results are garbage, only the time means something): bit 0 = no global loads, bit 1 = no
-  // twrites (v_perm + ds_write_b128), bit 2 = no fragment reads, bit 3 = no MFMAs, bit 4 = no barriers
-#ifndef PVRL_TN_ABLATE
-#define PVRL_TN_ABLATE 0
-#endif
   auto gload = [&](u32x4* r, int st) {
-    if (PVRL_TN_ABLATE & 1) return;
     if ((st + 1) * TS <= rows) {
       const char* b = ubase + (long)st * TS * ld2;
 #pragma unroll
@@ -311,7 +302,6 @@ __device__ __forceinline__ void tn_rt8_pair(const GemmTN& p, const int pair, cha
     }
   };
   auto twrite = [&](const u32x4* r, int j, char* slot) {   // column j of the lane's 8: gather its 8 m, store 16 B
-    if (PVRL_TN_ABLATE & 2) return;
     u32x4 o;
 #pragma unroll
     for (int d = 0; d < 4; ++d)
@@ -328,7 +318,6 @@ __device__ __forceinline__ void tn_rt8_pair(const GemmTN& p, const int pair, cha
   }
   const int pbase = wn * 2048, qbase = OPB + wk * 1024;
   auto rfrag = [&](const char* slot, int off, int h) {
-    if (PVRL_TN_ABLATE & 4) { opx8 z = (opx8)(op_t)0.5f; asm volatile("" : "+v"(z)); return z; }
     return *reinterpret_cast<const opx8*>(slot + off + h * 16384);
   };
 
@@ -343,7 +332,7 @@ __device__ __forceinline__ void tn_rt8_pair(const GemmTN& p, const int pair, cha
   ones2[0] = (op_t)1.0f; ones2[1] = (op_t)1.0f;
   auto lds_barrier = [&]() {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (!(PVRL_TN_ABLATE & 16)) __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
   };
   u32x4 ra[8];
@@ -375,10 +364,7 @@ __device__ __forceinline__ void tn_rt8_pair(const GemmTN& p, const int pair, cha
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) {
 #pragma unroll
-          for (int kt = 0; kt < 4; ++kt) {
-            if (PVRL_TN_ABLATE & 8) asm volatile("" :: "v"(qf[kt]), "v"(pf[nt]));
-            else acc[4 * half + nt][kt] = MFMA_16x16x32(qf[kt], pf[nt], acc[4 * half + nt][kt], 0, 0, 0);
-          }
+          for (int kt = 0; kt < 4; ++kt) acc[4 * half + nt][kt] = MFMA_16x16x32(qf[kt], pf[nt], acc[4 * half + nt][kt], 0, 0, 0);
           if (nt & 1) twrite(r, 4 * h + 2 * half + (nt >> 1), ws);
         }
       }

@@ -1218,12 +1218,7 @@ extern "C" int pvrl_mvit_pool_bwd(const void* dy, const void* conv_out, const vo
 #define DGRAD(SS) hipLaunchKernelGGL(pool_dgrad_kernel<SS>, dg, db, 0, s, (const op_t*)dc_scratch, g, w, (op_t*)dqkv)
 #define DGRAD_T(DD, SS) hipLaunchKernelGGL((pool_dgrad_t_kernel<DD, SS>), dim3(grid_for((long)B * H * Hh * Ww * 16)), db, 0, s, \
                                            (const op_t*)dc_scratch, g, w, (op_t*)dqkv)
-#ifndef PVRL_POOL_DGRAD_S
-#define PVRL_POOL_DGRAD_S 1                                     // 0: run-time strides everywhere (A/B builds)
-#endif
-    if (!PVRL_POOL_DGRAD_S && st == 1 && sh == 1 && sw == 1) DGRAD_T(true, 0);
-    else if (!PVRL_POOL_DGRAD_S && st == 1) DGRAD_T(false, 0);
-    else if (st == 1 && sh == 1 && sw == 1) DGRAD_T(true, 1);   // temporal stride 1: one 16-lane group per input column, sliding along t
+    if (st == 1 && sh == 1 && sw == 1) DGRAD_T(true, 1);   // temporal stride 1: one 16-lane group per input column, sliding along t
     else if (st == 1 && S == 2) DGRAD_T(false, 2);
     else if (st == 1 && S == 4) DGRAD_T(false, 4);
     else if (st == 1 && S == 8) DGRAD_T(false, 8);
@@ -1238,7 +1233,7 @@ extern "C" int pvrl_mvit_pool_bwd(const void* dy, const void* conv_out, const vo
   if (wb < 1) wb = 1;
   // temporal stride 1 (every MViTv2 pooling operator): the t-sliding form.  Before its nine neighbour loads were issued together
   // it lost to the 27-loads-at-once form on the big planes and on strided pooling; now it is ahead on every block of
-  // MViTv2-S (tools/probe/mvit_pool_times.py: 56 x 56 stride 1 880 -> 578 us, 28 x 28 stride 2 332 -> 252, 14 x 14 stride 2 116 -> 91)
+  // MViTv2-S (profiles/NOTES_rounds_1_3.md: 56 x 56 stride 1 880 -> 578 us, 28 x 28 stride 2 332 -> 252, 14 x 14 stride 2 116 -> 91)
   if (st == 1)
     hipLaunchKernelGGL(pool_wgrad_t_kernel, dim3((unsigned)wb), dim3(PW_CQ * PW_LANES), 0, s, (const op_t*)dc_scratch,
                        (const op_t*)qkv, g, (float*)workspace);

@@ -394,8 +394,7 @@ extern "C" int pvrl_mvit_rel_bwd(const float* drel, const void* Q, void* dQ, int
   // 2.4 / 1.9 / 2.8 / 4.2 ms per MViTv2-S step)
   const long nthr = (long)BH * qt * qh * qw * (HD / 12);
   if (nthr >= (1L << 31) - (1L << 20)) return PVRL_EINVAL;          // 32-bit index arithmetic in rel_bwd_q_kernel
-  static const int relq_lds = [] { const char* e = getenv("PVRL_RELQ_LDS"); return e ? (e[0] != '0') : 1; }();   // 0: A/B runs
-  if (relq_lds && nrows_h + nrows_w + nrows_t <= RELQ_MAXROWS && qh * kh <= RELQ_MAXIDX && qw * kw <= RELQ_MAXIDX && qt * kt <= RELQ_MAXIDX &&
+  if (nrows_h + nrows_w + nrows_t <= RELQ_MAXROWS && qh * kh <= RELQ_MAXIDX && qw * kw <= RELQ_MAXIDX && qt * kt <= RELQ_MAXIDX &&
       ((uintptr_t)Rh % 16) == 0 && ((uintptr_t)Rw % 16) == 0 && ((uintptr_t)Rt % 16) == 0) {
     // one 16-wave workgroup per CU (104 KB of tables), walking the queries grid-stride
     const unsigned grid = (unsigned)std::min<long>((nthr + 1023) / 1024, 256);

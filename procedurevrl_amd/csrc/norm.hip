@@ -14,7 +14,6 @@
 // 3.0e-4, profiles/r6_resid16_rounding.txt).  A row-major matrix is then described by TWO pointers (`Rows`): rows [0, rows16) live
 // in a 16-bit matrix, rows [rows16, M) in an fp32 one -- per LayerNorm pass over the 50k token rows: 77 instead of 154 MB for x,
 // for the incoming and for the outgoing residual gradient.  rows16 = 0 is the all-fp32 matrix of rounds 1-5.
-#include <cstdlib>
 #include "common.h"
 #include "../../include/pvrl.h"
 
@@ -126,17 +125,9 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const Rows x, const float* 
 
 // workgroups of a backward launch over M rows: one more than the rows need, so that a split matrix always has a workgroup for each part
 constexpr int LN_BWD_MAX_BLOCKS = 512;
-inline int ln_bwd_max_blocks() {        // PVRL_LN_BWD_BLOCKS: probe runs (read once)
-  static int n = 0;
-  if (n == 0) {
-    const char* e = getenv("PVRL_LN_BWD_BLOCKS");
-    n = e && atoi(e) >= 8 ? atoi(e) : LN_BWD_MAX_BLOCKS;
-  }
-  return n;
-}
 inline int ln_bwd_nblk(long M) {
   const long n = (M + 3) / 4 + 1;
-  return (int)(n < ln_bwd_max_blocks() ? n : ln_bwd_max_blocks());
+  return (int)(n < LN_BWD_MAX_BLOCKS ? n : LN_BWD_MAX_BLOCKS);
 }
 // ... of which the LAST nb_hi walk the fp32 rows [rows16, M)
 inline int ln_bwd_nblk_hi(long M, long rows16) {

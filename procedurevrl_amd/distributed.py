@@ -155,7 +155,7 @@ class GradReducer:
 
     Installs `engine.grad_hook`; during loss.backward() the hook fires after each block (last block first) and
     launches an async collective on that block's contiguous slice on a dedicated communication stream (ordered behind
-    the main stream and the weight-gradient side stream, and behind nothing later).  `finish()` reduces whatever is
+    the main stream, and behind nothing later).  `finish()` reduces whatever is
     left (embeddings, head, order transformer: they sit outside the block ranges) and makes the main stream wait.
     Averaging (1/world) is folded into the optimiser's `grad_scale`.
 
@@ -267,8 +267,7 @@ class GradReducer:
         return [dist.all_reduce(c, async_op=True)]
 
     def _reduce(self, a, b):
-        """async sum over ranks of flat[a:b], ordered after everything enqueued so far on the main stream and on the
-        engine's weight-gradient side stream"""
+        """async sum over ranks of flat[a:b], ordered after everything enqueued so far on the main stream"""
         gs = self.vt.grad_store()
         t = gs.flat[a:b]
         half = self.grad_comm == "bf16"
@@ -280,9 +279,6 @@ class GradReducer:
             return
         comm = self._comm_stream(t.device)
         comm.wait_event(torch.cuda.current_stream().record_event())
-        side = getattr(self.vt.engine, "_side", None)
-        if side is not None:
-            comm.wait_event(side.record_event())
         with torch.cuda.stream(comm):
             c = self._staging(gs, a, b) if half else t
             if half:

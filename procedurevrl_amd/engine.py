@@ -146,7 +146,7 @@ class GradStore:
         amax = torch.nan_to_num(g.abs().max(), nan=1.0, posinf=3e38).clamp(1e-30, 3e38)
         self.scale = torch.exp2(torch.floor(torch.log2(self.SCALE_TARGET / amax)).clamp(-100.0, 100.0)).reshape(1)
         self.inv = 1.0 / self.scale
-        self.inv_row = self.inv.expand(4096).contiguous()      # 1 / S as a GEMM epilogue's per-row scale (EncoderEngine._temporal_chain)
+        self.inv_row = self.inv.expand(4096).contiguous()      # 1 / S as a GEMM epilogue's per-row scale (EncoderEngine._temporal_chain_all)
         return g * self.scale
 
     def unscale(self):
@@ -250,8 +250,8 @@ class GraphReplay:
 
     The engine provides: _eager_forward(frames, training, save), _eager_backward(dfeat), _graph_key(frames, training,
     save), _enc_params() (the parameters whose gradients backward writes), `saved`, `grad_hook`, and consults
-    `self._capturing` ("fwd": refresh every weight copy inside the graph, "bwd": reuse them, and keep side-stream
-    operands alive until the join).  Optional: _bwd_begin / _bwd_block / _bwd_end + join_side_stream for staged capture.
+    `self._capturing` ("fwd": refresh every weight copy inside the graph, "bwd": reuse them).  Optional: _bwd_begin /
+    _bwd_block / _bwd_end for staged capture.
     """
     GRAPH_WARMUP = 2      # eager calls of a key before it is captured (lazy workspaces / caches settle)
     GRAPH_MAX_KEYS = 4    # captured (shape, mode) combinations kept; others run eagerly
@@ -308,6 +308,10 @@ class GraphReplay:
 
     def _bwd_group_end(self, state):
         """staged backward: a group of blocks is done -- an engine that defers work of its blocks finishes it here (default: nothing)"""
+
+    def join_side_stream(self):
+        """Callers that drive a backward stage by stage call this before reading its results.  Every engine issues all of its
+        work on the current stream, so there is nothing to wait for."""
 
     @staticmethod
     def _saved_copy(saved):
@@ -412,8 +416,7 @@ class GraphReplay:
                 graphs.append((graph, []))
             else:
                 # one graph per GROUP of `hook_group` blocks (the first also holds the final-norm stage, the last the embedding stage):
-                # the hook runs for a group's blocks after its replay.  A capture cannot end with side-stream work in flight, so each
-                # stage joins its weight gradients
+                # the hook runs for a group's blocks after its replay
                 state = None
                 i = nb - 1
                 while i >= 0:
@@ -427,8 +430,6 @@ class GraphReplay:
                         self._bwd_group_end(state)
                         if lo == 0:
                             self._bwd_end(state)
-                        else:
-                            self.join_side_stream()
                     graphs.append((graph, list(range(i, lo - 1, -1))))
                     i = lo - 1
         except Exception as e:          # never fatal: the eager launch sequence is the same kernels
@@ -460,15 +461,14 @@ class EncoderEngine(GraphReplay):
         self.saved = None
         self.grad_hook = None
         # ONE STREAM since round 5.  Until round 4 the weight-gradient GEMMs ran on a side stream next to the dgrad chain and the
-        # fused temporal maps W_e were built on it at the start of the forward (PVRL_WGRAD_OVERLAP=1 / PVRL_PREFETCH_FUSED=1 bring
-        # both back).  Measured (profiles/r5_hw_queues.txt, two passes): single stream 636.5 clips/s, W_e prefetch only 632.3, both
-        # 622.7 -- and only the single-stream step is independent of how HIP maps streams to hardware queues: with the side
-        # stream it is 58 ms instead of 51 at GPU_MAX_HW_QUEUES=6 (the branches of its graph truly co-run), the capture segfaults
-        # inside ROCm 7 at 1-2 queues, and under a foreign stream's long kernel (RCCL) it stalls behind whatever shares its queue
-        # (tools/probe/comm_cus_ab.py).  Grouped weight-gradient launches fill the chip on their own; there is nothing to overlap.
-        # the 768^3 GEMMs of the fused temporal branch (W_e per block in forward; dW_fc, dW_proj per block in backward) batched into
-        # one launch per dozen (ops.gemm_nt_batched): 36 tiles apiece cannot fill 256 CUs (PVRL_BATCH_FUSED=0: one launch each, A/B runs)
-        self.batch_fused = os.environ.get("PVRL_BATCH_FUSED", "1") == "1"
+        # fused temporal maps W_e were built on it at the start of the forward.  Measured (profiles/r5_hw_queues.txt, two passes):
+        # single stream 636.5 clips/s, W_e prefetch only 632.3, both 622.7 -- and only the single-stream step is independent of how
+        # HIP maps streams to hardware queues: with the side stream it is 58 ms instead of 51 at GPU_MAX_HW_QUEUES=6 (the branches of
+        # its graph truly co-run), the capture segfaults inside ROCm 7 at 1-2 queues, and under a foreign stream's long kernel (RCCL)
+        # it stalls behind whatever shares its queue (tools/probe/comm_cus_ab.py).  Grouped weight-gradient launches fill the chip on
+        # their own; there is nothing to overlap.
+        # the 768^3 GEMMs of the fused temporal branch (W_e per block in forward; dW_fc, dW_proj per block in backward) are batched into
+        # one launch per dozen (ops.gemm_nt_batched): 36 tiles apiece cannot fill 256 CUs
         # with a gradient hook (data parallel): blocks per group -- the hook runs (and the deferred launches go out, batched) once per
         # group of this many blocks instead of per block: four all-reduce rounds of ~135 MB per backward instead of twelve of 45
         self.hook_group = max(1, int(os.environ.get("PVRL_HOOK_GROUP", "3")))
@@ -476,9 +476,6 @@ class EncoderEngine(GraphReplay):
         self._fused_fresh = set()
         self._chain = []
         self._ln_defer = []
-        self.overlap_wgrad = os.environ.get("PVRL_WGRAD_OVERLAP", "0") == "1"
-        self.prefetch_fused = os.environ.get("PVRL_PREFETCH_FUSED", "0") == "1"
-        self._side = None
         self.group_wgrad = True       # one grouped launch for a block's seven weight gradients
         # the B cls rows' projection + MLP in fp32 on the master weights (csrc/cls_chain.hip; PVRL_CLS_FP32=0: A/B runs)
         self.cls_fp32 = os.environ.get("PVRL_CLS_FP32", "1") == "1"
@@ -498,10 +495,7 @@ class EncoderEngine(GraphReplay):
         # not exist turns the loss / gradients NaN (tests/e2e_checks.check_train_step_undefined_rows_nan_filled runs the suite's steps so).
         self.debug_nan_undefined = os.environ.get("PVRL_DEBUG_NAN_UNDEFINED", "0") == "1"
         self._wq = []
-        self._wpost = []
-        self._side_keep = []
         self._keep = None
-        self._fe_events = {}
         self._graph_init()            # HIP-graph replay of the step (GraphReplay)
         self._refreshed = False
         assert self.C == 768 and self.C // self.H == 64, "kernels are built for ViT-B (C=768, head_dim=64)"
@@ -571,7 +565,7 @@ class EncoderEngine(GraphReplay):
         temporal_fc), so  x + fc(rs * proj(o)) = x + rs * (o W_e^T + b_e) + b_fc  with  W_e = W_fc W_proj,  b_e = W_fc b_proj:
         ONE 50k-row GEMM forward (and one data-gradient / one weight-gradient GEMM backward) instead of two each.
         W_e is rebuilt from the bf16 operand copies whenever either weight changed (a 768^3 MFMA GEMM); the parameter
-        gradients are recovered from dW_e in backward (`_temporal_chain`)."""
+        gradients are recovered from dW_e in backward (`_temporal_chain_all`)."""
         wf, wp = blk.temporal_fc.weight, blk.temporal_attn.proj.weight
         e = self._w.get(("fused_t", id(wf)))
         if e is None:
@@ -579,8 +573,8 @@ class EncoderEngine(GraphReplay):
             self._w[("fused_t", id(wf))] = e
         ef, ep = self._weight(wf), self._weight(wp)
         ver = (ef.ver, ep.ver, blk.temporal_attn.proj.bias._version)
-        if self._capturing == "bwd" or id(blk) in self._fe_events or id(blk) in self._fused_fresh:     # (built a moment ago by
-            return e                                                     #  _prefetch_fused_temporal / _build_fused_all)
+        if self._capturing == "bwd" or id(blk) in self._fused_fresh:     # (built a moment ago by _build_fused_all)
+            return e
         if self._capturing == "fwd" or e.ver != ver or e.w is None:
             L = lib()
             we = ops.gemm_nt(ef.w, ep.t, L.PVRL_EPI_F32)                    # [out, in] = W_fc [out, mid] . W_proj [mid, in]
@@ -588,25 +582,6 @@ class EncoderEngine(GraphReplay):
             e.be = ops.gemv_rows(wf.detach(), blk.temporal_attn.proj.bias.detach(), out=e.be)                 # [out]
             e.ver = ver
         return e
-
-    def _prefetch_fused_temporal(self, device):
-        """W_e / b_e of every block depend on the weights only, yet building them where they are used puts a 768^3 GEMM, a
-        cast and a GEMV (~50 us on 36 CUs) in front of every block's temporal GEMM: 0.6 ms per forward on the critical
-        path.  They are built for all blocks on the side stream at the start of the forward, under the patch embedding and
-        the first block's LayerNorm / QKV / attention; each block waits for its own event."""
-        self._fe_events = {}
-        side = self.side_stream(device, force=True) if self.prefetch_fused and device.type == "cuda" else None
-        if side is None:
-            return
-        stale = [blk for blk in self.m.blocks if self._fused_temporal_stale(blk)]
-        if not stale:
-            return
-        ev0 = torch.cuda.current_stream().record_event()      # behind the weight-copy refresh
-        with torch.cuda.stream(side):
-            side.wait_event(ev0)
-            for blk in stale:
-                self._fused_temporal(blk)
-                self._fe_events[id(blk)] = side.record_event()      # (registered AFTER the build: see _fused_temporal)
 
     def _fused_temporal_stale(self, blk):
         if self._capturing == "fwd":
@@ -618,40 +593,10 @@ class EncoderEngine(GraphReplay):
         ep = self._w.get(id(blk.temporal_attn.proj.weight))
         return ef is None or ep is None or e.ver != (ef.ver, ep.ver, blk.temporal_attn.proj.bias._version)
 
-    def _temporal_chain(self, blk, gs, dwe, dbe):
-        """dW_e [out, in], db_e [out] (fp32, from the weight-gradient GEMM of the fused map) -> gradients of the four
-        parameters:  dW_fc = dW_e W_proj^T + db_e b_proj^T,  dW_proj = W_fc^T dW_e,  db_proj = W_fc^T db_e  (db_fc comes from the LayerNorm
-        backward's column sums).  Runs on the stream of the weight-gradient launch, right behind it."""
-        L = lib()
-        wf, wp = blk.temporal_fc.weight, blk.temporal_attn.proj.weight
-        ef, ep = self._weight(wf), self._weight(wp)
-        dwe_b, dwe_t = ops.cast_weight(dwe)                                   # bf16 [out, in] and [in, out]
-        # dW_e / db_e are in the backward's S-scaled units (fp16 flavour; their 16-bit copies above must stay mid-range); the scale
-        # is taken out where the four parameter gradients are written: a row scale of 1 / S in the GEMM epilogues, `gscale` below
-        rs = gs.inv_row if gs.inv is not None else None
-        # (gemm_nt_batched / rank1_add / gemv_rows take no `nonfinite` argument: checks=False keeps these parameters in the optimiser's scan)
-        tg = [(gs.target(lin_w, fused=True, checks=False), A, W) for lin_w, A, W in ((wf, dwe_b, ep.w), (wp, ef.t, dwe_t))]   # [out,mid] = dW_e.W_p^T ; [mid,in] = W_f^T.dW_e
-        if self.batch_fused and tg[0][0][1] == tg[1][0][1]:                   # both in one launch (72 tiles instead of 2 x 36)
-            beta = tg[0][0][1]
-            ops.gemm_nt_batched([dict(A=A, W=W, rowscale=rs, out0=g, aux=g if beta else None) for (g, _), A, W in tg],
-                                L.PVRL_EPI_RESID_F32 if beta else L.PVRL_EPI_F32)
-        else:
-            for (g, beta), A, W in tg:
-                if beta == 0.0:
-                    ops.gemm_nt(A, W, L.PVRL_EPI_F32, rowscale=rs, out0=g)
-                else:
-                    ops.gemm_nt(A, W, L.PVRL_EPI_RESID_F32, rowscale=rs, aux=g, out0=g)
-        # proj's bias rides through temporal_fc too (b_e = W_fc b_proj): its share of dW_fc is the outer product db_e x b_proj
-        ops.rank1_add(gs.target(wf, fused=True, checks=False)[0], dbe, blk.temporal_attn.proj.bias.detach(), gscale=gs.inv)
-        gb, beta = gs.target(blk.temporal_attn.proj.bias, fused=True, checks=False)
-        ops.gemv_rows(ef.t, dbe, out=gb, beta=beta, gscale=gs.inv)            # [mid] = W_fc^T db_e (bf16 operand copy)
-
     def _build_fused_all(self):
         """W_e = W_fc W_proj (and b_e) of every block whose weights changed, at the start of a forward: ONE batched launch of the twelve
         768^3 GEMMs and one of the twelve casts instead of a 16.6-us GEMM + a cast in front of every block's temporal GEMM."""
         self._fused_fresh = set()
-        if not self.batch_fused or self.prefetch_fused:
-            return
         stale = [blk for blk in self.m.blocks if self._fused_temporal_stale(blk)]
         if len(stale) < 2:
             return
@@ -685,12 +630,16 @@ class EncoderEngine(GraphReplay):
             self._fused_fresh.add(id(blk))
 
     def _temporal_chain_all(self, gs):
-        """`_temporal_chain` for every block queued by the backward (no gradient hook installed: nobody needs a block's gradients
-        before the end): the 2 x 12 GEMMs dW_fc = dW_e W_proj^T, dW_proj = W_fc^T dW_e as batched launches, the twelve casts as one."""
+        """dW_e [out, in], db_e [out] (fp32, from the weight-gradient GEMM of each fused map the backward queued) -> gradients of the
+        four parameters:  dW_fc = dW_e W_proj^T + db_e b_proj^T,  dW_proj = W_fc^T dW_e,  db_proj = W_fc^T db_e  (db_fc comes from the
+        LayerNorm backward's column sums).  Nobody needs a block's gradients before the end of the backward (of its group, under a
+        gradient hook): the 2 x 12 GEMMs as batched launches, the twelve casts as one."""
         chain, self._chain = self._chain, []
         if not chain:
             return
         L = lib()
+        # dW_e / db_e are in the backward's S-scaled units (fp16 flavour; their 16-bit copies must stay mid-range); the scale is taken
+        # out where the four parameter gradients are written: a row scale of 1 / S in the GEMM epilogues, `gscale` below
         rs = gs.inv_row if gs.inv is not None else None
         dev = chain[0][1].device
         C = self.C
@@ -702,7 +651,8 @@ class EncoderEngine(GraphReplay):
         for (blk, dwe, dbe), (_, dwe_b, dwe_t) in zip(chain, items):
             wf, wp = blk.temporal_fc.weight, blk.temporal_attn.proj.weight
             ef, ep = self._weight(wf), self._weight(wp)
-            for lin_w, A, W in ((wf, dwe_b, ep.w), (wp, ef.t, dwe_t)):
+            for lin_w, A, W in ((wf, dwe_b, ep.w), (wp, ef.t, dwe_t)):       # [out,mid] = dW_e.W_p^T ; [mid,in] = W_f^T.dW_e
+                # (gemm_nt_batched / rank1_add / gemv_rows take no `nonfinite` argument: checks=False keeps these parameters in the optimiser's scan)
                 g, beta = gs.target(lin_w, fused=True, checks=False)
                 groups[beta].append(dict(A=A, W=W, rowscale=rs, out0=g, aux=g if beta else None))
         if groups[0.0]:
@@ -724,59 +674,18 @@ class EncoderEngine(GraphReplay):
     def grad_store(self):
         return self.m.grad_store()
 
-    # ------------------------------------------------------------------ side stream for weight gradients
-    def side_stream(self, device, force=False):
-        """Nothing in backward depends on a weight gradient until the optimiser step, while the data-gradient chain
-        (dgrad GEMM -> LayerNorm bwd -> attention bwd ...) is strictly serial.  With `overlap_wgrad` the weight-gradient GEMMs are
-        issued on a second HIP stream: they fill CUs left idle by the ragged last wave of the big-tile dgrad GEMMs
-        and overlap the HBM-bound LayerNorm / cast kernels.  (`force`: the stream itself, for the forward's W_e prefetch.)"""
-        if not self.overlap_wgrad and not force:
-            return None
-        if self._side is None or self._side.device != device:
-            self._side = torch.cuda.Stream(device=device)
-        return self._side
-
-    def _wgrad(self, dy, xin, dw, dbias, beta, post=None, gscale=None, nonfinite=None):
-        """queue dW = beta*dW + gscale * dy^T xin (and dbias); `flush_wgrads` issues what is queued.  `post` (optional callable)
-        runs right behind the launch on the same stream (consumers of dW)."""
+    # ------------------------------------------------------------------ weight gradients
+    def _wgrad(self, dy, xin, dw, dbias, beta, gscale=None, nonfinite=None):
+        """queue dW = beta*dW + gscale * dy^T xin (and dbias); `flush_wgrads` issues what is queued."""
         self._wq.append((dy, xin, dw, dbias, beta, gscale, nonfinite))
-        if post is not None:
-            self._wpost.append(post)
         if not self.group_wgrad:
             self.flush_wgrads()
 
     def flush_wgrads(self):
-        """Issue the queued weight gradients as one grouped launch (ops.gemm_tn_grouped) -- on the side stream when
-        overlap_wgrad, ordered after everything the current stream has produced so far."""
+        """Issue the queued weight gradients as one grouped launch (ops.gemm_tn_grouped)."""
         q, self._wq = self._wq, []
-        post, self._wpost = self._wpost, []
-        if not q and not post:
-            return
-        side = self.side_stream(q[0][0].device if q else torch.device("cuda", torch.cuda.current_device()))
-        if side is None:
+        if q:
             ops.gemm_tn_grouped(q, ws_tag="tn")
-            for f in post:
-                f()
-            return
-        ev = torch.cuda.current_stream().record_event()
-        with torch.cuda.stream(side):
-            side.wait_event(ev)
-            ops.gemm_tn_grouped(q, ws_tag="tn_side")
-            for f in post:
-                f()
-            done = side.record_event()
-        # The operands must outlive the side-stream kernels.  Tensor.record_stream would do that, but every pending
-        # record makes EACH later allocation poll its event (measured: torch.empty 2 -> 52 us with ~170 records in flight,
-        # 20 ms of host time per step); instead the references are parked here until the launch's event has completed,
-        # or until join_side_stream() has ordered the main stream behind the side stream.
-        self._side_keep.append((done, [t for pr in q for t in pr[:4] + pr[5:6] if t is not None]))
-        while not self._capturing and self._side_keep and self._side_keep[0][0].query():
-            self._side_keep.pop(0)        # (no event queries while capturing: there everything is held until the join)
-
-    def join_side_stream(self):
-        if self._side is not None:
-            torch.cuda.current_stream().wait_stream(self._side)
-        self._side_keep.clear()      # later allocations are ordered behind the join on the current stream
 
     # ------------------------------------------------------------------ drop path
     def _droppath_all(self, B, N, T, device, training):
@@ -841,7 +750,6 @@ class EncoderEngine(GraphReplay):
         self._refresh_weights()
         self._refreshed = True
         self._build_fused_all()
-        self._prefetch_fused_temporal(frames.device)
         B, _, T, HI, WI = frames.shape
         Wp = WI // 16
         N = (HI // 16) * Wp
@@ -934,9 +842,6 @@ class EncoderEngine(GraphReplay):
         else:
             x1 = _X.new(R, B, C, dev, False)
         fe = self._fused_temporal(blk)          # proj then temporal_fc as one linear map
-        ev = self._fe_events.pop(id(blk), None)
-        if ev is not None:                      # W_e of this block was built on the side stream (_prefetch_fused_temporal)
-            torch.cuda.current_stream().wait_event(ev)
         ops.gemm_nt(o_t, fe.w, epi_res, bias=fe.be, rowscale=s1_tok, bias2=P(blk.temporal_fc.bias),
                     aux=x0.p, out0=x1.p)
         if not split:
@@ -1027,9 +932,6 @@ class EncoderEngine(GraphReplay):
 
     def _graph_reset_host_state(self):
         self._wq = []
-        self._wpost = []
-        self._side_keep = []
-        self._fe_events = {}
         self._chain = []
         self._ln_defer = []
         self._fused_fresh = set()
@@ -1135,7 +1037,6 @@ class EncoderEngine(GraphReplay):
         self._acc(gs, tim_p, dtime.unsqueeze(0))
         self.flush_wgrads()
         self._finish_deferred(gs)
-        self.join_side_stream()
         if gs.scale is not None:
             gs.end_scaled()
         self.saved = None
@@ -1167,7 +1068,7 @@ class EncoderEngine(GraphReplay):
             self._wgrad(dy, xin, dw, dbias, bw, gscale=gs.inv, nonfinite=gs.bad)
 
         # (the 7-us reduces of the LayerNorm partials are deferred: one launch for the whole backward, or per group of blocks under a gradient hook)
-        defer = self._ln_defer if self.batch_fused else None
+        defer = self._ln_defer
 
         def lnbwd(dh, x, st, ln, dx_in, dx_out, dxs=None, dxs_scale=None, dxsum=None, dxsum_beta=None):
             (dg, bg), (db, _) = gs.target(ln.weight, fused=True), gs.target(ln.bias, fused=True)
@@ -1248,11 +1149,8 @@ class EncoderEngine(GraphReplay):
         fe = self._fused_temporal(blk)
         dwe = torch.empty((C, C), device=dev, dtype=F32)
         dbe = torch.empty(C, device=dev, dtype=F32)
-        if self.batch_fused:                                   # nobody needs this block's gradients before the end of the backward (of its
-            self._wgrad(dz, s["o_t"], dwe, dbe, 0.0)           # group, under a gradient hook): the chains run batched in _finish_deferred
-            self._chain.append((blk, dwe, dbe))
-        else:
-            self._wgrad(dz, s["o_t"], dwe, dbe, 0.0, post=lambda b=blk, w=dwe, v=dbe: self._temporal_chain(b, gs, w, v))
+        self._wgrad(dz, s["o_t"], dwe, dbe, 0.0)               # the chain runs batched in _finish_deferred (_temporal_chain_all)
+        self._chain.append((blk, dwe, dbe))
         dot = ops.gemm_nt(dz, fe.t, L.PVRL_EPI_BF16)
         if T == 8:
             dqkv_t = ops.attn_t8_bwd(s["qkv_t"], dot, B * N, H, self.scale)

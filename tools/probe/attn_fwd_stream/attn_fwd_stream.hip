@@ -25,7 +25,7 @@ namespace {
 
 #ifndef PVRL_FS_TRACE
 #define PVRL_FS_TRACE 0      // probe builds only: the waves of workgroup 8 stamp the cycle counter at the seams of their third item; dumped over
-#endif                       // the tail of the lse array (tools/probe/attn_bwd_ab.py ftrace)
+#endif                       // the tail of the lse array
 #if PVRL_FS_TRACE
 #define FS_STAMP(k) do { if (tracing) stamps[k] = (unsigned)__builtin_readcyclecounter(); } while (0)
 #else

@@ -11,7 +11,7 @@
 // Why it loses although it removes 190 of the VALU kernel's 264 instructions per frame: a wave walks its 8 frames serially with the
 // next frame's loads one frame (~500-1,000 cycles) ahead -- less than a memory round trip -- and the register budget (60 VGPRs of
 // diagonal operands) leaves neither deeper prefetch nor more than 12 waves per CU to cover it; the VALU kernel is issue-bound
-// (tools/pmc_pool.sh: every wave waits 60 % of its cycles while its SIMD's issue slots are ~95 % used by the 4-5 resident waves)
+// (SQ_WAIT_ANY vs SQ_WAVE_CYCLES: every wave waits 60 % of its cycles while its SIMD's issue slots are ~95 % used by the 4-5 resident waves)
 // but keeps 16-20 waves per CU.  Halving the MFMA time (v1 -> v2) and halving the load segment size changed nothing: neither pipe
 // nor the texture path is the limit.  Per frame a wave runs one dependent chain -- loads -> 15 MFMAs (five deep per accumulator) ->
 // accumulator read -> two cross-lane reductions -> LDS exchange + barrier -> rsqrt -> convert -> stores -- of ~2,000 cycles with ~500 cycles
@@ -21,7 +21,7 @@
 // LDS-DMA several frames ahead would fix the memory side only.
 
 // ---- Round 3: the depthwise convolution on the matrix pipe ------------------------------------------------------------------------
-// PMC (tools/pmc_pool.sh, block 4): the VALU forms above are instruction-issue-bound -- 2,590 VALU instructions per wave for 3,072
+// PMC (SQ counters, block 4): the VALU forms above are instruction-issue-bound -- 2,590 VALU instructions per wave for 3,072
 // outputs, every wave waiting 60 % of its cycles while its SIMD's issue slots are ~95 % taken by the four resident waves.  Of the
 // 264 instructions per frame only 81 are the (packed) FMAs; 54 unpack bf16, 55 move operands into pairs, the rest is addresses and
 // LayerNorm.  A depthwise tap IS a matrix product with a diagonal weight matrix,
