@@ -287,6 +287,35 @@ int pvrl_grad_scale_begin(const float* g, int64_t n, float target, float* out, f
  * step that consumed it, whatever loop calls it. */
 int pvrl_flag_roll(float* flag, float* total, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Mixup / CutMix fine-tuning (lib/datasets/mixup.py; tools/train_net.py:137-143).  The host draws the reference's numpy random
+ * numbers (procedurevrl_amd/mixup.py) into a mix plan of one descriptor per clip; clip b is always mixed with clip B-1-b.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define PVRL_MIX_NONE 0      /* the clip is left as it is (its weights are 1 and 0)                                   */
+#define PVRL_MIX_BLEND 1     /* x[b] = x[b] * lam + x[partner] * lam_partner, each product and the sum rounded in fp32  */
+#define PVRL_MIX_CUT 2       /* x[b][:, t0:t1, h0:h1, :] = x[partner][:, t0:t1, h0:h1, :]                              */
+typedef struct {
+  int32_t partner;           /* B - 1 - b */
+  int32_t kind;              /* PVRL_MIX_* */
+  int32_t t0, t1, h0, h1;    /* the cut box as drawn on img_shape[-2:] = (H, W) and applied to a [C, T, H, W] clip as
+                              * [:, t0:t1, h0:h1]: it slices frames and rows (clamped to T and H), all columns */
+  float lam, lam_partner;    /* the weights of the clip and of its partner, in the blend and in the mixed target */
+} pvrl_mix_desc;
+/* Apply a mix plan IN PLACE to an fp32 clip batch x [B, C, T, H, W] (B even; desc: B device descriptors, desc[b].partner ==
+ * B-1-b).  One thread owns the same element of clip b and of clip B-1-b, so both are read before either is written: every
+ * source is the unmixed batch.  Cut elements are copied; only elements a descriptor touches are read or written. */
+int pvrl_mix_clips(float* x, const pvrl_mix_desc* desc, int64_t B, int64_t C, int64_t T, int64_t H, int64_t W, void* stream);
+/* Soft-target cross entropy (timm SoftTargetCrossEntropy): row_loss[i] = sum_j -t_ij * log_softmax(x_i)_j and
+ * dx[i] = grad_scale * (S_i * softmax(x_i) - t_i), S_i = sum_j t_ij (not assumed to be 1).  x fp32 [rows, K].  The target is
+ *   dense        target fp32 [rows, K] (ldt), labels / desc null; or
+ *   synthesised  target null: t_ij = lam_i * y(labels[i])_j + lam_partner_i * y(labels[partner_i])_j with y(l)_j = on if j == l
+ *                else off (each product and the sum rounded in fp32, as mixup_target's one-hots); labels int64 [rows] and
+ *                desc [rows] on the device.  A label outside [0, K) gives a row of `off`.
+ * dx may be null (loss only). */
+int pvrl_soft_ce(const float* x, int64_t ldx, int64_t rows, int64_t K, const float* target, int64_t ldt,
+                 const int64_t* labels, const pvrl_mix_desc* desc, float on, float off, float grad_scale, float* row_loss,
+                 float* dx, int64_t ldd, void* stream);
+
 /* softmax over the rows of an fp32 logit matrix: the eval-mode output `self.softmax(x)` (vit.py:355-356, mvit.py:203-204) */
 int pvrl_softmax_rows_f32(const float* x, int64_t ldx, float* y, int64_t ldy, int64_t M, int64_t N, void* stream);
 /* exact-erf GELU on a small fp32 tensor (time_mlp, tfm_model.py:89-94): out = gelu(x), or out = dy * gelu'(x) when dy != 0 */

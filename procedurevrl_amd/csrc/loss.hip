@@ -5,6 +5,7 @@
 //     (ties kept, duplicated top values counted as often as they occur); renormalise;
 //     loss1 = KLDivLoss(batchmean)(log_softmax(pred), teacher)     tools/train_net.py:152-160
 //   * loss2 = MSELoss(mean)(mse[0], mse[1]), gradient to BOTH operands  tools/train_net.py:161
+//   * soft-target cross entropy of the Mixup fine-tuning loop           tools/train_net.py:137-143
 // One workgroup per logit row (K = 9871 step candidates): the row is streamed from HBM twice
 // (teacher, student), everything else (softmax, top-5 selection, KL, gradient) is fused.
 #include "common.h"
@@ -247,6 +248,57 @@ __global__ __launch_bounds__(256) void milnce_grad_kernel(const float* __restric
   }
 }
 
+__device__ __forceinline__ float mix_target(float y1, float w1, float y2, float w2) {
+#pragma clang fp contract(off)   // two rounded products and a rounded sum, as torch's `y1 * lam + y2 * (1 - lam)`
+  const float u = y1 * w1, v = y2 * w2;
+  return u + v;
+}
+
+// Soft-target cross entropy (timm SoftTargetCrossEntropy, tools/train_net.py:137-143 under MIXUP): one workgroup per row.
+//   row_loss = sum_j t_j * (m + log(se) - x_j);  dx_j = grad_scale * (S * exp(x_j - m) / se - t_j),  S = sum_j t_j
+// The EPIC noun targets of mixup_target do not sum to 1 (97 / 300-wide one-hots, off = smoothing / NUM_CLASSES), so S is summed.
+// target == null: the mixed target is synthesised from the hard labels and the mix plan, never written to memory.
+__global__ __launch_bounds__(256) void soft_ce_kernel(const float* __restrict__ x, long ldx, int rows, int K,
+                                                      const float* __restrict__ target, long ldt,
+                                                      const int64_t* __restrict__ labels, const pvrl_mix_desc* __restrict__ desc,
+                                                      float on, float off, float grad_scale, float* __restrict__ row_loss,
+                                                      float* __restrict__ dx, long ldd) {
+  __shared__ float red[4];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const float* xr = x + (long)row * ldx;
+  long l1 = -1, l2 = -1;
+  float w1 = 1.f, w2 = 0.f;
+  if (!target) {
+    int p = desc[row].partner;
+    if (p < 0 || p >= rows) p = row;
+    l1 = labels[row];
+    l2 = labels[p];
+    w1 = desc[row].lam;
+    w2 = desc[row].lam_partner;
+  }
+  // y1 * lam + y2 * (1 - lam) of mixup_target, y = the on / off one-hot
+  auto tgt = [&](int k) -> float {
+    if (target) return target[(long)row * ldt + k];
+    return mix_target(k == l1 ? on : off, w1, k == l2 ? on : off, w2);
+  };
+  float mx = -INFINITY;
+  for (int k = tid; k < K; k += 256) mx = fmaxf(mx, xr[k]);
+  mx = block_reduce(mx, red, true);
+  float se = 0.f, ts = 0.f;
+  for (int k = tid; k < K; k += 256) { se += expf(xr[k] - mx); ts += tgt(k); }
+  se = block_reduce(se, red, false);
+  ts = block_reduce(ts, red, false);
+  const float lz = mx + logf(se), inv = 1.0f / se;
+  float loss = 0.f;
+  for (int k = tid; k < K; k += 256) {
+    const float v = xr[k], t = tgt(k);
+    loss += t * (lz - v);
+    if (dx) dx[(long)row * ldd + k] = grad_scale * (ts * (expf(v - mx) * inv) - t);
+  }
+  loss = block_reduce(loss, red, false);
+  if (tid == 0) row_loss[row] = loss;
+}
+
 
 // row softmax over fp32 logits (eval-mode output of the wrappers, lib/models/vit.py:355-356): one workgroup per row
 __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restrict__ x, long ldx, float* __restrict__ y,
@@ -336,6 +388,17 @@ extern "C" int pvrl_mse(const float* a, const float* b, int64_t n, float grad_sc
                         void* stream) {
   if (n <= 0 || !a || !b) return PVRL_EINVAL;
   hipLaunchKernelGGL(mse_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a, b, (long)n, grad_scale, loss, da, db);
+  PVRL_LAUNCH_CHECK();
+  return PVRL_OK;
+}
+
+extern "C" int pvrl_soft_ce(const float* x, int64_t ldx, int64_t rows, int64_t K, const float* target, int64_t ldt,
+                            const int64_t* labels, const pvrl_mix_desc* desc, float on, float off, float grad_scale,
+                            float* row_loss, float* dx, int64_t ldd, void* stream) {
+  if (rows <= 0) return PVRL_OK;
+  if (!x || !row_loss || K <= 0 || (!target && (!labels || !desc))) return PVRL_EINVAL;
+  hipLaunchKernelGGL(soft_ce_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, x, (long)ldx, (int)rows, (int)K,
+                     target, (long)ldt, labels, desc, on, off, grad_scale, row_loss, dx, (long)ldd);
   PVRL_LAUNCH_CHECK();
   return PVRL_OK;
 }

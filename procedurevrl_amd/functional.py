@@ -179,6 +179,28 @@ def mse_loss(a, b):
     return MSELossFn.apply(a, b)
 
 
+class SoftTargetCEFn(torch.autograd.Function):
+    """timm SoftTargetCrossEntropy (tools/train_net.py:137-143): mean_i sum_j -t_ij log_softmax(x_i)_j, forward and gradient in
+    one kernel; the target is dense or synthesised from hard labels + a mix plan (ops.soft_ce)."""
+
+    @staticmethod
+    def forward(ctx, x, target, labels, plan):
+        rows = x.shape[0]
+        row_loss, dx = ops.soft_ce(x.contiguous(), target=None if target is None else target.detach().contiguous(), labels=labels,
+                                   plan=plan, grad_scale=1.0 / rows)
+        ctx.save_for_backward(dx)
+        return row_loss.sum() / rows
+
+    @staticmethod
+    def backward(ctx, g):
+        (dx,) = ctx.saved_tensors
+        return dx * g, None, None, None
+
+
+def soft_target_cross_entropy(x, target=None, labels=None, plan=None):
+    return SoftTargetCEFn.apply(x, target, labels, plan)
+
+
 class MatmulNTFn(torch.autograd.Function):
     """a @ b.t() in fp32 with gradients to both operands (similarity matrix of the contrastive loss)."""
 

@@ -785,3 +785,51 @@ def gelu_f32(x, dy=None):
     out = torch.empty_like(x)
     L.call("pvrl_gelu_f32", _ptr(x), _ptr(dy), _ptr(out), x.numel(), _stream())
     return out
+
+
+# ----------------------------------------------------------------------------------------
+# Mixup / CutMix (mixup.py draws the plan on the host)
+# ----------------------------------------------------------------------------------------
+def mix_clips(x, plan):
+    """Apply a mixup.MixPlan in place to fp32 clips [B, C, T, H, W] and return them; a transform.DecodedClips batch is
+    materialised with frames_u8_to_f32 first (the returned tensor is then a new one)."""
+    from .transform import DecodedClips
+    if isinstance(x, DecodedClips):
+        x = frames_u8_to_f32(x)
+    if not (x.is_cuda and x.dtype == F32 and x.is_contiguous() and x.dim() == 5):
+        raise PvrlError(f"mix_clips expects a contiguous fp32 [B, C, T, H, W] device tensor, got {x.dtype} {tuple(x.shape)}")
+    B, C, T, H, W = x.shape
+    if plan.batch_size != B or B % 2:
+        raise PvrlError(f"mix plan of {plan.batch_size} clips for a batch of {B} (mixup needs an even batch)")
+    if [int(v) for v in plan.partner] != list(range(B - 1, -1, -1)):
+        raise PvrlError("pvrl_mix_clips pairs clip b with clip B-1-b")
+    if plan.is_identity:
+        return x
+    lib().call("pvrl_mix_clips", _ptr(x), _ptr(plan.device_descriptors(x.device)), B, C, T, H, W, _stream())
+    return x
+
+
+def soft_ce(x, target=None, labels=None, plan=None, grad_scale=None):
+    """Soft-target cross entropy of fp32 logits [rows, K] -> (row_loss [rows], dx or None).  The target is dense fp32
+    [rows, K] (`target`) or synthesised from int64 hard `labels` [rows] and a mixup.MixPlan of `rows` clips."""
+    L = lib()
+    _chk2d(x, F32)
+    rows, K = x.shape
+    if target is not None:
+        _chk2d(target, F32)
+        if tuple(target.shape) != (rows, K):
+            raise PvrlError(f"soft target {tuple(target.shape)} for logits {(rows, K)}")
+        desc = lab = None
+        on = off = 0.0
+    else:
+        if plan is None or labels is None or plan.batch_size != rows or labels.numel() != rows:
+            raise PvrlError("the synthesised soft target needs the hard labels and the mix plan of every row")
+        lab = labels.reshape(-1).to(torch.int64).contiguous()
+        desc = plan.device_descriptors(x.device)
+        on, off = plan.on, plan.off
+    row_loss = torch.empty(rows, device=x.device, dtype=F32)
+    dx = torch.empty_like(x) if grad_scale is not None else None
+    L.call("pvrl_soft_ce", _ptr(x), _ld(x), rows, K, _ptr(target), _ld(target) if target is not None else 0, _ptr(lab),
+           _ptr(desc), float(on), float(off), float(grad_scale if grad_scale is not None else 0.0), _ptr(row_loss), _ptr(dx),
+           _ld(dx) if dx is not None else 0, _stream())
+    return row_loss, dx

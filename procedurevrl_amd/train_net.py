@@ -5,7 +5,10 @@ Kept from the reference: per-iteration LR set (:123-124), `meta` reshape (:146),
 next log point), the accumulation branch to GLOBAL_BATCH_SIZE (:176-192, folded into the optimiser's
 grad_scale), top-k error on the logits vs a dummy label (:226-231), the fine-tuning branch (:149-150, 163-169: cross entropy /
 `smooth` on model(inputs); EPIC-Kitchens verb + noun heads with their accuracies :195-222), json_stats logging, checkpoint /
-auto-resume.  Not built: MIXUP (no shipped ProcedureVRL config enables it).
+auto-resume, and MIXUP (:137-143, the EPIC-Kitchens fine-tuning config enables it): a `mixup.Mixup` built from the cfg every
+iteration draws the reference's numpy random numbers into a mix plan, `pvrl_mix_clips` mixes the clips in place, the loss is
+the soft-target cross entropy of the mixed targets (`pvrl_soft_ce`, synthesised from the hard labels and the plan), and the
+accuracies are taken on the hard labels (:140,171).
 Changed by design: gradients are reduced by `GradReducer` (flat buffer, overlapped with backward) instead of DDP,
 the three metric scalars are one all-reduce, and the host reads them only every LOG_PERIOD iterations instead of
 `.item()`-syncing every iteration (:234-236)."""
@@ -14,6 +17,7 @@ import math
 import os
 import time
 
+import numpy as np
 import torch
 
 from . import checkpoint as cu
@@ -21,6 +25,7 @@ from . import distributed as du
 from . import optimizer as optim
 from .build import build_model
 from .datasets import DevicePrefetcher, construct_loader, shuffle_dataset
+from .mixup import mixup_from_cfg
 from .vit import pretrain_loss
 
 
@@ -69,13 +74,27 @@ def is_pretraining(cfg):
     return cfg.TRAIN.LABEL_EMB != "" and cfg.TRAIN.TEXT != ""
 
 
-def finetune_loss(preds, labels, cfg):
-    """tools/train_net.py:126-136,163-169: cross entropy (or `smooth`) on the logits; EPIC-Kitchens: the mean of the verb and
-    the noun loss.  Returns (loss, per-task losses or None)."""
-    from .losses import get_loss_func
-    if cfg.MIXUP.ENABLED:
-        raise NotImplementedError("MIXUP.ENABLED (timm Mixup, tools/train_net.py:137-143) is not built; no shipped ProcedureVRL config enables it")
-    loss_fun = LabelSmoothingCrossEntropy(0.2) if cfg.MODEL.LOSS_FUNC == "smooth" else get_loss_func(cfg.MODEL.LOSS_FUNC)(reduction="mean")
+def mixup_active(cfg):
+    """tools/train_net.py:126-143: MIXUP.ENABLED takes effect unless MODEL.LOSS_FUNC is `smooth` or `kldiv`, which come first"""
+    return bool(cfg.MIXUP.ENABLED) and cfg.MODEL.LOSS_FUNC not in ("smooth", "kldiv")
+
+
+def finetune_loss(preds, labels, cfg, mix=None):
+    """tools/train_net.py:126-143,163-169: cross entropy (or `smooth`) on the logits; EPIC-Kitchens: the mean of the verb and
+    the noun loss.  Under MIXUP (`mixup_active`) `mix` is the batch's
+    mixup.MixPlan and the loss is the soft-target cross entropy against the mixed targets of the hard `labels`.
+    Returns (loss, per-task losses or None)."""
+    from .losses import SoftTargetCrossEntropy, get_loss_func
+    if mixup_active(cfg):
+        if mix is None:
+            raise NotImplementedError("MIXUP.ENABLED: a hard-label loss is undefined under mixup; pass the batch's mix plan "
+                                      "(mixup.Mixup) as finetune_loss(preds, labels, cfg, mix=plan)")
+        soft = SoftTargetCrossEntropy()
+        loss_fun = lambda x, y: soft(x, labels=y, plan=mix)
+    elif cfg.MODEL.LOSS_FUNC == "smooth":
+        loss_fun = LabelSmoothingCrossEntropy(0.2)
+    else:
+        loss_fun = get_loss_func(cfg.MODEL.LOSS_FUNC)(reduction="mean")
     if isinstance(labels, dict) and cfg.TRAIN.DATASET == "Epickitchens":
         lv, ln = loss_fun(preds[0], labels["verb"]), loss_fun(preds[1], labels["noun"])
         return 0.5 * (lv + ln), (lv, ln)
@@ -126,8 +145,12 @@ def train_epoch(train_loader, model, optimizer, reducer, cur_epoch, cfg, max_ite
             pred, teacher_pred, mse = model([inputs, meta])
             loss, loss1, loss2 = pretrain_loss(pred, teacher_pred, mse, cfg)
         else:                                                  # fine-tuning (train_net.py:149-150,163-169): logits -> cross entropy
+            plan = None
+            if mixup_active(cfg):
+                # train_net.py:137-143: a fresh Mixup per iteration, the inputs mixed in place, the hard labels kept for the metrics
+                inputs, plan = mixup_from_cfg(cfg)(inputs)
             pred = model(inputs)
-            loss, task_losses = finetune_loss(pred, labels, cfg)
+            loss, task_losses = finetune_loss(pred, labels, cfg, mix=plan)
         first_micro = not accumulate or cur_iter % num_iters == 0
         if first_micro:
             optimizer.zero_grad(set_to_none=True)
@@ -322,8 +345,17 @@ def is_eval_epoch(cfg, cur_epoch):
     return (cur_epoch + 1) % cfg.TRAIN.EVAL_PERIOD == 0
 
 
+def check_mixup_cfg(cfg):
+    """MIXUP.ENABLED on the fine-tuning branch: one logit row per clip (no shipped config combines mixup with MODEL.NUM_SEG)."""
+    if mixup_active(cfg) and not is_pretraining(cfg) and cfg.MODEL.NUM_SEG > 0:
+        raise NotImplementedError(f"MIXUP.ENABLED with MODEL.NUM_SEG {cfg.MODEL.NUM_SEG}: the mix plan pairs one logit row per clip "
+                                  "(no shipped config combines them)")
+
+
 def train(cfg, max_iters=None):
+    check_mixup_cfg(cfg)
     du.init_distributed_training(cfg)
+    np.random.seed(cfg.RNG_SEED)                               # train_net.py:428 (the Mixup draws)
     torch.manual_seed(cfg.RNG_SEED)
     model = build_model(cfg)
     optimizer = optim.construct_optimizer(model, cfg)
