@@ -124,10 +124,14 @@ class GeluStore(torch.autograd.Function):
 class AttnMFMA(torch.autograd.Function):
     """softmax(q k^T * scale) v as csrc/attn_mfma.hip computes it on 16-bit q, k, v [.., S, d]:
     forward: e = exp(scale * (s - max)) rounded as the second MFMA's operand, o = (R(e) v) / sum(e);
-    backward: P = exp(scale*s - lse) in fp32, D = rowsum(dO * O_stored), dS = R(P * (dP - D) * scale), dV = R(P)^T dO."""
+    backward: P = exp(scale*s - lse) in fp32, D = rowsum(dO * O_stored), dS = R(P * (dP - D) * scale), dV = R(P)^T dO.
+    `mask` (optional, bool, broadcastable to the scores, True = key not seen: causal / key padding) sets those scores to -inf in front
+    of the maximum, as the masked kernel forms do; no row may be masked entirely."""
     @staticmethod
-    def forward(ctx, q, k, v, scale):
+    def forward(ctx, q, k, v, scale, mask=None):
         s = q @ k.transpose(-2, -1)
+        if mask is not None:
+            s = s.masked_fill(mask, float("-inf"))
         m = s.amax(-1, keepdim=True)
         e = torch.exp((s - m) * scale)
         den = e.sum(-1, keepdim=True)
@@ -142,7 +146,7 @@ class AttnMFMA(torch.autograd.Function):
         dp = do @ v.transpose(-2, -1)
         d = (do * o).sum(-1, keepdim=True)
         ds = _rnd(p * (dp - d) * ctx.scale)
-        return ds @ k, ds.transpose(-2, -1) @ q, _rnd(p).transpose(-2, -1) @ do, None
+        return ds @ k, ds.transpose(-2, -1) @ q, _rnd(p).transpose(-2, -1) @ do, None, None
 
 
 def _value_of(exact, rounded):

@@ -675,8 +675,8 @@ def check_attn_mfma_spatial():
     from procedurevrl_amd import ops
     g = torch.Generator().manual_seed(7)
     out = []
-    # (11, 8, 196, 12): 88 sequences x 12 heads = 1,056 (sequence, head) items -> the persistent LDS-DMA forward kernel,
-    # ragged over the 256 workgroups (some walk 5 items, some 4) and over the XCDs (11 sequences each)
+    # (11, 8, 196, 12): 88 sequences x 12 heads = 1,056 (sequence, head) items -> more than the persistent fused backward's 256
+    # workgroups, ragged over them (some walk 5 items, some 4) and over the XCDs (11 sequences each); the forward is one workgroup per item
     # (1, 2, 256, 2): a 256^2 crop's 257-token spatial sequences (long-sequence instantiation of the two-pass kernels);
     # (3, 4, 120, 2): 121 tokens -> four query blocks in the fused backward's run-time-loop form, 12 sequences x 2 heads
     for (B, T, N, H) in [(2, 4, 16, 2), (2, 8, 196, 12), (11, 8, 196, 12), (1, 2, 256, 2), (3, 4, 120, 2)]:
