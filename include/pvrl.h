@@ -397,7 +397,12 @@ int pvrl_mvit_rel_bwd(const float* drel, const void* Q, void* dQ, int64_t BH, in
  * relp = the operand form written by pvrl_mvit_rel_fwd with out_scale = 1 / scale.  keymap = the 0/1 matrix
  * E[key][j] (j = h(key), kh + w(key), kh + kw + t(key)) of the key geometry as MFMA tile images, a function of
  * (kt, kh, kw) only: build it once with pvrl_mvit_attn_keymap into pvrl_mvit_attn_keymap_bytes bytes and reuse it.
- * lse / delta fp32 [B*H][Lq+1]; drel fp32 [B*H][Lq][kh+kw+kt] (gradient w.r.t. the unscaled rel).  The dK / dV kernel
+ * lse / delta fp32 [B*H][Lq+1]; drel fp32 [B*H][Lq][kh+kw+kt] (gradient w.r.t. the unscaled rel).
+ * lse is a BASE-2 logarithm: with c = scale * log2(e) and s[k] the unscaled score of key k (q.k + rel bias / scale),
+ * lse[q] = c * max_k s[k] + log2(sum_k exp2(c * (s[k] - max_k s[k]))) = log2(sum_k exp(logit[k])); the natural-log logsumexp is
+ * lse * ln 2.  The backward expects the forward's values unchanged.
+ * delta is an OUTPUT of the backward (rowsum(dO * (o - q)) per query, written by its first kernel and read by its second), not an
+ * input: pass scratch of the size of lse.  The dK / dV kernel
  * shares the query range out over workgroups (fp32 partials in `workspace`, pvrl_mvit_attn_bwd_workspace_bytes) and
  * reduces deterministically. */
 int64_t pvrl_mvit_attn_keymap_bytes(int64_t kt, int64_t kh, int64_t kw);

@@ -329,7 +329,8 @@ def model_variant(q, k, v, do, scale, mask, operand):
 # metric and verdicts
 # ---------------------------------------------------------------------------------------------------------------------
 def rowerr(x, ref):
-    """-> (max over rows of ||x_row - ref_row|| / rms of ||ref_row||, flat index of the worst row); x, ref [..., 64]; inf when x is not finite"""
+    """-> (max over rows of ||x_row - ref_row|| / rms of ||ref_row||, flat index of the worst row); x, ref [..., W], a row = the last dimension;
+    inf when x is not finite"""
     x, ref = x.double().reshape(-1, x.shape[-1]), ref.double().reshape(-1, ref.shape[-1])
     e = (x - ref).pow(2).sum(-1).sqrt()
     e = torch.where(torch.isfinite(e), e, torch.full_like(e, float("inf")))
@@ -355,29 +356,33 @@ def _where(c, items, flat, S):
     return f"(sequence {item // c.H}, head {item % c.H}, token {flat % S}" + (f"; draw {draw})" if draw else ")")
 
 
-def judge_tensor(c, name, x, ref, mod, items, agg_bound, zero_floor=0.0):
-    """the tolerance rule of the module docstring for one output tensor [n_items, S', 64] -> [Finding, Finding] (row statistic, aggregate).
-    agg_bound: a number (the `randn` regime: today's flat bound) or None (follow the model).  zero_floor: see `fp32_zero_floor`."""
+def judge_tensor(c, name, x, ref, mod, items, agg_bound, zero_floor=0.0, where=None):
+    """the tolerance rule of the module docstring for one output tensor [n_items, S', W] (a row = one vector of W: 64 here, 96 / J in
+    tests/pool_attn_checks.py) -> [Finding, Finding] (row statistic, aggregate).
+    agg_bound: a number (the `randn` regime: today's flat bound) or None (follow the model).  zero_floor: see `fp32_zero_floor`.
+    where: (flat row index, rows per item) -> text naming the row, for cases that are not a `Case` (default: `_where` of c, items)."""
     S = x.shape[1]
+    loc = where if where is not None else (lambda flat, S: _where(c, items, flat, S))
     if ref.abs().max().item() < 1e-10:          # identically zero reference (dq with equal keys): absolute comparison with the model
         xm, mm = x.abs().max().item(), mod.abs().max().item()
         xm = xm if math.isfinite(xm) else float("inf")
-        i = int(torch.nan_to_num(x.abs().reshape(-1, 64).amax(-1), nan=float("inf")).argmax())
+        i = int(torch.nan_to_num(x.abs().reshape(-1, x.shape[-1]).amax(-1), nan=float("inf")).argmax())
         bound = ROW_FACTOR * mm + zero_floor
         return [Finding(name + " max|x| (zero reference)", xm <= bound, xm, bound,
-                        f"model max {mm:.3e}, fp32 floor {zero_floor:.1e}, ratio {xm / max(mm, 1e-300):.2f}, worst row {_where(c, items, i, S)}")]
+                        f"model max {mm:.3e}, fp32 floor {zero_floor:.1e}, ratio {xm / max(mm, 1e-300):.2f}, worst row {loc(i, S)}")]
     rk, i = rowerr(x, ref)
     rm, _ = rowerr(mod, ref)
     ak, am = agg(x, ref), agg(mod, ref)
     ab = ROW_FACTOR * am if agg_bound is None else agg_bound
     return [Finding(name + " rowerr", rk <= ROW_FACTOR * rm, rk, ROW_FACTOR * rm,
-                    f"model rowerr {rm:.3e}, ratio {rk / max(rm, 1e-300):.2f}, worst row {_where(c, items, i, S)}"),
+                    f"model rowerr {rm:.3e}, ratio {rk / max(rm, 1e-300):.2f}, worst row {loc(i, S)}"),
             Finding(name + " aggregate L2", ak <= ab, ak, ab, f"model aggregate {am:.3e}, ratio {ak / max(am, 1e-300):.2f}")]
 
 
-def judge_lse(c, lse, ref, items):
-    """lse [n_items, S'] against ref["lse"] (fp64), yardstick ref["lse32"]"""
+def judge_lse(c, lse, ref, items, where=None):
+    """lse [n_items, S'] against ref["lse"] (fp64), yardstick ref["lse32"]; where: as in `judge_tensor`"""
     S = lse.shape[1]
+    loc = where if where is not None else (lambda flat, S: _where(c, items, flat, S))
     r64, r32 = ref["lse"][:, :S], ref["lse32"][:, :S]
     y = (r32.double() - r64).abs().max().item()
     ulp = torch.exp2(torch.floor(torch.log2(r64.abs().clamp_min(1.0))) - 23)
@@ -386,7 +391,7 @@ def judge_lse(c, lse, ref, items):
     slack = err - (LSE_FACTOR * y + LSE_ULPS * ulp)
     i = int(slack.argmax())
     e, b = err.reshape(-1)[i].item(), (LSE_FACTOR * y + LSE_ULPS * ulp).reshape(-1)[i].item()
-    return [Finding("lse abs error", e <= b, e, b, f"fp32 yardstick {y:.3e}, max error {err.max().item():.3e}, worst entry {_where(c, items, i, S)}")]
+    return [Finding("lse abs error", e <= b, e, b, f"fp32 yardstick {y:.3e}, max error {err.max().item():.3e}, worst entry {loc(i, S)}")]
 
 
 def agg_bounds(c, regime, operand=None):
