@@ -350,6 +350,9 @@ int pvrl_layernorm_g_bwd(const void* dy, int64_t lddy, int dy_is_f32, const floa
 /* attention_pool (attention.py:14-48) for mode "conv": depthwise Conv3d(96 ch, kernel 3x3x3, padding 1, stride st,sh,sw, no
  * bias; weight fp32 [96][27]) + LayerNorm(96) on one of q / k / v taken in place from the packed qkv activation (bf16
  * [B*T*Hh*Ww + B][ld], columns col0 + h*96 ..); the cls token skips the conv.  y / conv_out: [B*H][To*Ho*Wo + 1][96] bf16.
+ * conv_out holds the conv output ROUNDED ONCE to the 16-bit operand type (the cls row: the token itself); y is the LayerNorm of
+ * the unrounded fp32 conv, while the backward recomputes its LayerNorm statistics (mean, rstd) from conv_out, i.e. from the
+ * rounded values -- hand the backward the conv_out the forward wrote, nothing else.
  * Backward writes this tensor's slice of dqkv and ACCUMULATES dw [96][27], dgamma, dbeta; dc_scratch: bf16, size of y;
  * workspace >= pvrl_mvit_pool_bwd_workspace_bytes() holds per-workgroup fp32 partials of dw that a second kernel sums in a
  * fixed order (same-address fp32 atomics from 8 XCDs cost ~0.5 us each and made every call ~200 us). */
@@ -365,7 +368,9 @@ int pvrl_mvit_pool_bwd(const void* dy, const void* conv_out, const void* qkv, vo
 /* MaxPool3d skip of MultiScaleBlock (attention.py:537-552): kernel (1,s+1,s+1), stride (1,s,s), padding (0,(s+1)/2,..),
  * fp32 token matrix in / out, cls rows copied.  Backward routes to the first maximum (torch semantics).
  * `argmax` (optional, uint8 [B*T*Ho*Wo][C]): the forward records each window's winner (window-local index), the backward
- * then routes by it (4 + 16 bytes per window) instead of re-scanning the windows of x (790 -> ~150 us at 25k tokens x 32 clips). */
+ * then routes by it (4 + 16 bytes per window) instead of re-scanning the windows of x (790 -> ~150 us at 25k tokens x 32 clips).
+ * The byte holds yy * (s + 1) + xx, so the argmax form needs s <= 14: a larger s with argmax != NULL is PVRL_EINVAL from both
+ * entry points (argmax == NULL, the re-scanning form, has no such limit). */
 int pvrl_mvit_maxpool_fwd(const float* x, int64_t ldi, int64_t B, int64_t T, int64_t H, int64_t W, int64_t s, int64_t C,
                           float* y, int64_t ldo, void* argmax, void* stream);
 int pvrl_mvit_maxpool_bwd(const float* x, int64_t ldi, const float* dy, int64_t ldo, int64_t B, int64_t T, int64_t H,

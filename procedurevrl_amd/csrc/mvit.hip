@@ -620,10 +620,9 @@ __global__ __launch_bounds__(256) void pool_ln_bwd_kernel(const op_t* __restrict
   }
 }
 
-// data gradient of the depthwise conv: dX[b, l_in, h, c] = sum_taps dc[out(l_in, tap)][c] * w[c][tap]
-// S > 0: spatial stride S (a power of two) with temporal stride 1 -- every shipped MViT config -- so the 39 stride
-// divisions / remainders per token become shifts and masks and the token decomposition is 32-bit; S = 0: any strides.
-template <int S>
+// data gradient of the depthwise conv: dX[b, l_in, h, c] = sum_taps dc[out(l_in, tap)][c] * w[c][tap], any strides.  The launcher
+// takes this form for temporal stride > 1 only (temporal stride 1 -- every shipped MViT config -- goes to pool_dgrad_t_kernel below,
+// which has the compile-time spatial strides).
 __global__ __launch_bounds__(256) void pool_dgrad_kernel(const op_t* __restrict__ dc, PoolGeom g,
                                                          const float* __restrict__ w, op_t* __restrict__ dqkv) {
   __shared__ float ws[27 * HD];
@@ -631,7 +630,7 @@ __global__ __launch_bounds__(256) void pool_dgrad_kernel(const op_t* __restrict_
   __syncthreads();
   const int sub = threadIdx.x & 15, c0 = sub * 6;
   const int Lo = g.To * g.Ho * g.Wo, L = g.T * g.Hh * g.Ww;
-  const int st = S ? 1 : g.st, sh = S ? S : g.sh, sw = S ? S : g.sw;
+  const int st = g.st, sh = g.sh, sw = g.sw;
   const unsigned ntok = (unsigned)((long)g.B * g.H * L);          // < 2^31 (checked by the launcher)
   const unsigned wg = (unsigned)xcd_remap((int)blockIdx.x, (int)gridDim.x);     // contiguous tokens per XCD (see pool_fwd_kernel)
   for (unsigned tok = (wg * 256u + threadIdx.x) >> 4; tok < ntok; tok += (gridDim.x * 256u) >> 4) {
@@ -642,20 +641,20 @@ __global__ __launch_bounds__(256) void pool_dgrad_kernel(const op_t* __restrict_
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       const int tn = ti + 1 - a;
-      if (tn < 0 || (S ? 0 : tn % st)) continue;
-      const int to = S ? tn : tn / st;
+      if (tn < 0 || tn % st) continue;
+      const int to = tn / st;
       if (to >= g.To) continue;
 #pragma unroll
       for (int yy = 0; yy < 3; ++yy) {
         const int yn = yi + 1 - yy;
-        if (yn < 0 || (S ? (yn & (S - 1)) : yn % sh)) continue;
-        const int yo = S ? yn / S : yn / sh;
+        if (yn < 0 || yn % sh) continue;
+        const int yo = yn / sh;
         if (yo >= g.Ho) continue;
 #pragma unroll
         for (int xx = 0; xx < 3; ++xx) {
           const int xn = xi + 1 - xx;
-          if (xn < 0 || (S ? (xn & (S - 1)) : xn % sw)) continue;
-          const int xo = S ? xn / S : xn / sw;
+          if (xn < 0 || xn % sw) continue;
+          const int xo = xn / sw;
           if (xo >= g.Wo) continue;
           float v[6];
           ld6(dc + ((long)bh * (Lo + 1) + ((long)to * g.Ho + yo) * g.Wo + xo) * HD + c0, v);
@@ -1201,6 +1200,8 @@ extern "C" int pvrl_mvit_pool_bwd(const void* dy, const void* conv_out, const vo
   hipStream_t s = (hipStream_t)stream;
   const long Lo = (long)g.To * g.Ho * g.Wo;
   const long ntok = (long)B * H * (Lo + 1);
+  const long nin = (long)B * H * T * Hh * Ww;
+  if (nin >= (1L << 27)) return PVRL_EINVAL;          // 16 lanes per token, 32-bit token arithmetic in the kernels; refused before anything is launched
   long blocks = (ntok * 16 + 255) / 256;
   if (blocks > PLN_MAX_WG) blocks = PLN_MAX_WG;
   float* lnpart = (float*)workspace + (long)PW_MAX_WG * 27 * HD;
@@ -1210,12 +1211,9 @@ extern "C" int pvrl_mvit_pool_bwd(const void* dy, const void* conv_out, const vo
   hipLaunchKernelGGL(partials_add_kernel, dim3((2 * HD + PADD_OUT - 1) / PADD_OUT), dim3(256), 0, s, (const float*)lnpart, (int)blocks,
                      2 * HD, dgamma, dbeta, HD);
   PVRL_LAUNCH_CHECK();
-  const long nin = (long)B * H * T * Hh * Ww;
-  if (nin >= (1L << 27)) return PVRL_EINVAL;          // 16 lanes per token, 32-bit token arithmetic in the kernel
   {
     const dim3 dg(grid_for(nin * 16)), db(256);
     const int S = (st == 1 && sh == sw && (sh == 1 || sh == 2 || sh == 4 || sh == 8)) ? (int)sh : 0;
-#define DGRAD(SS) hipLaunchKernelGGL(pool_dgrad_kernel<SS>, dg, db, 0, s, (const op_t*)dc_scratch, g, w, (op_t*)dqkv)
 #define DGRAD_T(DD, SS) hipLaunchKernelGGL((pool_dgrad_t_kernel<DD, SS>), dim3(grid_for((long)B * H * Hh * Ww * 16)), db, 0, s, \
                                            (const op_t*)dc_scratch, g, w, (op_t*)dqkv)
     if (st == 1 && sh == 1 && sw == 1) DGRAD_T(true, 1);   // temporal stride 1: one 16-lane group per input column, sliding along t
@@ -1224,8 +1222,7 @@ extern "C" int pvrl_mvit_pool_bwd(const void* dy, const void* conv_out, const vo
     else if (st == 1 && S == 8) DGRAD_T(false, 8);
     else if (st == 1) DGRAD_T(false, 0);
 #undef DGRAD_T
-    else if (S == 2) DGRAD(2); else if (S == 4) DGRAD(4); else if (S == 8) DGRAD(8); else DGRAD(0);
-#undef DGRAD
+    else hipLaunchKernelGGL(pool_dgrad_kernel, dg, db, 0, s, (const op_t*)dc_scratch, g, w, (op_t*)dqkv);   // temporal stride > 1
   }
   PVRL_LAUNCH_CHECK();
   long wb = (B * H * Lo + PW_LANES * 16 - 1) / (PW_LANES * 16);      // >= 16 tokens per lane: 2,592 global atomics per block
@@ -1247,6 +1244,8 @@ extern "C" int pvrl_mvit_pool_bwd(const void* dy, const void* conv_out, const vo
   return PVRL_OK;
 }
 
+// the argmax byte of a channel holds yy * k + xx with k = s + 1: k * k - 1 <= 255 needs k <= 15
+constexpr int MAXPOOL_ARGMAX_MAX_S = 14;
 static int maxpool_geom(MaxPoolGeom& g, int64_t B, int64_t T, int64_t H, int64_t W, int64_t s, int64_t C, int64_t ldi,
                         int64_t ldo) {
   if (B <= 0 || T <= 0 || H <= 0 || W <= 0 || s < 2 || C <= 0 || (C % 4) || (ldi % 4) || (ldo % 4) || ldi < C || ldo < C)
@@ -1261,7 +1260,7 @@ static int maxpool_geom(MaxPoolGeom& g, int64_t B, int64_t T, int64_t H, int64_t
 extern "C" int pvrl_mvit_maxpool_fwd(const float* x, int64_t ldi, int64_t B, int64_t T, int64_t H, int64_t W, int64_t s,
                                      int64_t C, float* y, int64_t ldo, void* argmax, void* stream) {
   MaxPoolGeom g;
-  if (!x || !y || maxpool_geom(g, B, T, H, W, s, C, ldi, ldo)) return PVRL_EINVAL;
+  if (!x || !y || maxpool_geom(g, B, T, H, W, s, C, ldi, ldo) || (argmax && s > MAXPOOL_ARGMAX_MAX_S)) return PVRL_EINVAL;
   const long total = ((long)B * T * g.Ho * g.Wo + B) * (C >> 2);
   if (total >= (1L << 31) - (1L << 24)) return PVRL_EINVAL;          // 32-bit index arithmetic in the kernel
   hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, g, y,
@@ -1273,7 +1272,7 @@ extern "C" int pvrl_mvit_maxpool_fwd(const float* x, int64_t ldi, int64_t B, int
 extern "C" int pvrl_mvit_maxpool_bwd(const float* x, int64_t ldi, const float* dy, int64_t ldo, int64_t B, int64_t T,
                                      int64_t H, int64_t W, int64_t s, int64_t C, float* dx, const void* argmax, void* stream) {
   MaxPoolGeom g;
-  if (!x || !dy || !dx || maxpool_geom(g, B, T, H, W, s, C, ldi, ldo)) return PVRL_EINVAL;
+  if (!x || !dy || !dx || maxpool_geom(g, B, T, H, W, s, C, ldi, ldo) || (argmax && s > MAXPOOL_ARGMAX_MAX_S)) return PVRL_EINVAL;
   // (no zero fill: the gather kernel writes every element.  An earlier scatter version zeroed dx with hipMemsetAsync, whose
   //  memset node in a captured HIP graph did not re-zero the buffer on replay -- ROCm 7.2 -- so gradients accumulated
   //  across replays; nothing on a captured path uses hipMemset* any more.)
