@@ -316,6 +316,41 @@ int pvrl_soft_ce(const float* x, int64_t ldx, int64_t rows, int64_t K, const flo
                  const int64_t* labels, const pvrl_mix_desc* desc, float on, float off, float grad_scale, float* row_loss,
                  float* dx, int64_t ldd, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * RandAugment of decoded uint8 clips (lib/datasets/autoaugment.py `rand_augment_transform`, applied per frame through PIL at
+ * lib/datasets/epickitchens.py:149-162).  The host draws the reference's random numbers (procedurevrl_amd/randaugment.py)
+ * into one descriptor per frame and layer; the kernels reproduce Pillow's pixels bit for bit.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define PVRL_RA_NONE 0           /* the frame is copied (the op's probability draw failed, or it is a no-op)              */
+#define PVRL_RA_AFFINE 1         /* Image.transform(AFFINE, c[0..5]): Rotate, ShearX/Y, TranslateX/YRel; fill outside       */
+#define PVRL_RA_AUTOCONTRAST 2   /* ImageOps.autocontrast: per-channel table from the histogram                            */
+#define PVRL_RA_EQUALIZE 3       /* ImageOps.equalize: per-channel table from the histogram                                */
+#define PVRL_RA_INVERT 4         /* 255 - v                                                                                */
+#define PVRL_RA_POSTERIZE 5      /* keep the iarg[0] most significant bits                                                 */
+#define PVRL_RA_SOLARIZE 6       /* v < iarg[0] ? v : 255 - v                                                              */
+#define PVRL_RA_SOLARIZE_ADD 7   /* v < iarg[1] ? min(255, v + iarg[0]) : v                                                */
+#define PVRL_RA_COLOR 8          /* Image.blend(luma image, frame, c[0])                                                   */
+#define PVRL_RA_CONTRAST 9       /* Image.blend(mean luma, frame, c[0])                                                    */
+#define PVRL_RA_BRIGHTNESS 10    /* Image.blend(black, frame, c[0])                                                        */
+#define PVRL_RA_SHARPNESS 11     /* Image.blend(ImageFilter.SMOOTH of the frame, frame, c[0])                              */
+#define PVRL_RA_BILINEAR 2       /* resample modes of PVRL_RA_AFFINE: PIL's Image.BILINEAR / Image.BICUBIC                 */
+#define PVRL_RA_BICUBIC 3
+typedef struct {
+  int32_t kind;              /* PVRL_RA_* */
+  int32_t resample;          /* PVRL_RA_BILINEAR / PVRL_RA_BICUBIC (PVRL_RA_AFFINE only) */
+  int32_t iarg[2];           /* integer arguments of the table ops */
+  double c[6];               /* PVRL_RA_AFFINE: PIL's inverse map, source = (c0 x + c1 y + c2, c3 x + c4 y + c5) at pixel centres,
+                              * computed on the host as PIL computes it; enhance ops: c[0] = the factor */
+} pvrl_ra_desc;
+/* Apply `layers` ops to every frame of uint8 [frames, H, W, 3] `in` -> `out` (same shape; `in` is only read, and is not `out`).
+ * desc: [layers][frames] device descriptors; layer l reads what layer l-1 wrote (`tmp`, a third buffer of the same size, is
+ * needed when layers > 1).  fill_r/g/b: the colour PVRL_RA_AFFINE writes where its source position lies outside the frame.  hist:
+ * int32 [frames][4][256] workspace (cleared here, per layer).  Three stream nodes per layer whatever the descriptors say: clear
+ * the workspace, histograms for the frames whose op reads them, apply.  W % 4 != 0 or a buffer that is not dword-aligned
+ * takes the one-pixel-per-item form. */
+int pvrl_rand_augment_u8(const void* in, void* out, void* tmp, const pvrl_ra_desc* desc, int64_t frames, int64_t layers, int64_t H,
+                         int64_t W, int fill_r, int fill_g, int fill_b, int32_t* hist, void* stream);
+
 /* softmax over the rows of an fp32 logit matrix: the eval-mode output `self.softmax(x)` (vit.py:355-356, mvit.py:203-204) */
 int pvrl_softmax_rows_f32(const float* x, int64_t ldx, float* y, int64_t ldy, int64_t M, int64_t N, void* stream);
 /* exact-erf GELU on a small fp32 tensor (time_mlp, tfm_model.py:89-94): out = gelu(x), or out = dy * gelu'(x) when dy != 0 */

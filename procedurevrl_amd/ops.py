@@ -833,3 +833,28 @@ def soft_ce(x, target=None, labels=None, plan=None, grad_scale=None):
            _ptr(desc), float(on), float(off), float(grad_scale if grad_scale is not None else 0.0), _ptr(row_loss), _ptr(dx),
            _ld(dx) if dx is not None else 0, _stream())
     return row_loss, dx
+
+
+# ----------------------------------------------------------------------------------------
+# RandAugment (randaugment.py draws the plan on the host)
+# ----------------------------------------------------------------------------------------
+def rand_augment_u8(frames_u8, plan):
+    """Apply a randaugment.RandAugPlan to decoded clips uint8 [B, T, H, W, 3] on the GPU -> a new tensor of the same shape,
+    bit-equal to the reference's per-frame PIL RandAugment; `frames_u8` is left as it is."""
+    if not (frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous() and frames_u8.dim() == 5
+            and frames_u8.shape[-1] == 3):
+        raise PvrlError(f"rand_augment_u8 expects a contiguous uint8 [B, T, H, W, 3] device tensor, got {frames_u8.dtype} "
+                        f"{tuple(frames_u8.shape)} on {frames_u8.device}")
+    B, T, H, W, _ = frames_u8.shape
+    if (plan.batch_size, plan.num_frames, plan.height, plan.width) != (B, T, H, W):
+        raise PvrlError(f"RandAugment plan for {plan.batch_size} clips of {plan.num_frames} frames of {plan.height}x{plan.width}, "
+                        f"batch {(B, T, H, W)}")
+    out = torch.empty_like(frames_u8)
+    L = plan.num_layers
+    tmp = torch.empty_like(frames_u8) if L > 1 else None
+    hist = torch.empty(B * T * 4 * 256, device=frames_u8.device, dtype=torch.int32)
+    desc = plan.device_descriptors(frames_u8.device)
+    r, g, b = plan.fill
+    lib().call("pvrl_rand_augment_u8", _ptr(frames_u8), _ptr(out), _ptr(tmp), _ptr(desc), B * T, L, H, W, int(r), int(g), int(b),
+               _ptr(hist), _stream())
+    return out

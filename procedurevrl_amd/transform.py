@@ -93,3 +93,23 @@ class DecodedClips:
 
     def float(self):
         return self
+
+
+def decoded_train_batch(cfg, frames_u8):
+    """A training batch of decoded clips, uint8 [B, T, H0, W0, 3] -> DecodedClips, with the draws of the reference's
+    loader made per clip in its order (lib/datasets/epickitchens.py:149-192).  With DATA.USE_RAND_AUGMENT every clip draws
+    its seed, its RandAugment plan and then its scale / crop / flip (`randaugment.epic_train_clip_draws`), and the frames
+    (on the GPU) are augmented by `ops.rand_augment_u8` before they are wrapped: augmented frames are just frames.
+    Without it only `spatial_sampling_params` draws."""
+    B, T, H0, W0, _ = frames_u8.shape
+    d = cfg.DATA
+    if d.USE_RAND_AUGMENT:
+        from . import ops
+        from .randaugment import RandAugPlan, epic_train_clip_draws
+        draws = [epic_train_clip_draws(cfg, T, H0, W0) for _ in range(B)]
+        frames_u8 = ops.rand_augment_u8(frames_u8, RandAugPlan([plan for plan, _ in draws]))
+        params = [p for _, p in draws]
+    else:
+        params = [spatial_sampling_params(H0, W0, -1, d.TRAIN_JITTER_SCALES[0], d.TRAIN_JITTER_SCALES[1], d.TRAIN_CROP_SIZE,
+                                          d.RANDOM_FLIP, d.INV_UNIFORM_SAMPLE) for _ in range(B)]
+    return DecodedClips(frames_u8, params, d.MEAN, d.STD, d.TRAIN_CROP_SIZE)

@@ -163,6 +163,31 @@ def main():
         us = timeit(lambda: ops.cast_scale(x, None))
         rows.append(("cast_scale [GB/s]", us, M * C * 6 / us / 1e3))
 
+    if want("randaug"):
+        # RandAugment at the EPIC-Kitchens per-GPU shape (4 clips x 32 frames x 256 x 456), every frame with two applied ops
+        # cycling through the 15 increasing transforms at magnitude 10, both signs and resample modes.  The rate counts one read
+        # and one write of the clip per layer (the histogram pass and the gathers' neighbours come on top).
+        from procedurevrl_amd import randaugment as ra
+        Bc, Tc, Hc, Wc = 4, 32, 256, 456
+        arg = {"Rotate": 30.0, "ShearX": 0.3, "ShearY": 0.3, "TranslateXRel": 0.45, "TranslateYRel": 0.45, "PosterizeIncreasing": 0,
+               "SolarizeIncreasing": 0, "SolarizeAdd": 110, "ColorIncreasing": 1.9, "ContrastIncreasing": 1.9,
+               "BrightnessIncreasing": 1.9, "SharpnessIncreasing": 1.9}
+
+        def op(i):
+            name = ra.RAND_INCREASING_TRANSFORMS[i % 15]
+            a = arg.get(name)
+            if name in ra.GEOMETRIC and (i // 15) % 2:
+                a = -a
+            elif name.endswith("Increasing") and isinstance(a, float) and (i // 15) % 2:
+                a = 2.0 - a
+            return ra.resolve_op(name, () if a is None else (a,), (ra.BILINEAR, ra.BICUBIC)[(i // 30) % 2], Wc, Hc)
+        clips = [ra.ClipPlan(None, [[op(b * Tc + t), op(7 * (b * Tc + t) + 3)] for t in range(Tc)], (115, 115, 115), Wc, Hc)
+                 for b in range(Bc)]
+        plan = ra.RandAugPlan(clips)
+        fr = torch.randint(0, 256, (Bc, Tc, Hc, Wc, 3), device=DEV, dtype=torch.uint8, generator=g)
+        us = timeit(lambda: ops.rand_augment_u8(fr, plan))
+        rows.append(("randaug u8 4x32x256x456, 2 layers [GB/s]", us, 4.0 * fr.numel() / us / 1e3))
+
     for name, us, rate in rows:
         print(f"{name:42s} {us:9.1f} us   {rate:9.1f} {'TFLOP/s' if 'GB/s' not in name else 'GB/s'}")
 
