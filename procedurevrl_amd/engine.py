@@ -179,17 +179,6 @@ class GradStore:
         return inv
 
 
-class _W:
-    """bf16 operand copies of one weight matrix: `w` = [N, K] for forward, `t` = [K, N] for the data gradient."""
-    __slots__ = ("w", "t", "ver", "be")
-
-    def __init__(self):
-        self.w = None
-        self.t = None
-        self.ver = -1
-        self.be = None      # fused temporal map only: fp32 [N] bias W_fc b_proj
-
-
 class _X:
     """One stage of the encoder's residual stream (or of its gradient): patch rows `p` [R, C], cls rows `c` [B, C] fp32.
     Split stream (EncoderEngine.resid16, round 6): `p` is its own tensor in the 16-bit operand type -- GEMM residual epilogues
@@ -456,7 +445,7 @@ class EncoderEngine(GraphReplay):
         self.H = model.num_heads
         self.scale = (self.C // self.H) ** -0.5
         self.eps = model.ln_eps
-        self._w = {}
+        self.weights = model.weights      # weights.WeightCache: the 16-bit operand copies, shared with the head and the text tower
         self._grads = None
         self.saved = None
         self.grad_hook = None
@@ -502,24 +491,8 @@ class EncoderEngine(GraphReplay):
 
     # ------------------------------------------------------------------ weights
     def _weight(self, p, need_t=True):
-        e = self._w.get(id(p))
-        if e is None:
-            e = _W()
-            self._w[id(p)] = e
-        # the fused optimiser updates trainable parameters through its flat buffer (no _version bump) and advances
-        # weights_epoch instead; frozen parameters (text tower) only change through versioned in-place copies
-        ver = (p._version, getattr(self.m, "weights_epoch", 0) if p.requires_grad else 0, p.data_ptr())
-        if self._capturing == "bwd":      # the forward graph of the same step refreshed the copies
-            assert e.w is not None and (e.t is not None or not need_t)
-            return e
-        if (self._capturing == "fwd" and not self._refreshed) or e.ver != ver or e.w is None or e.w.device != p.device:
-            w2 = p.detach().reshape(p.shape[0], -1).contiguous()
-            same = e.w is not None and e.w.device == p.device
-            e.w, t = ops.cast_weight(w2, out=e.w if same else None, out_t=e.t if same else None, need_t=need_t)
-            if need_t:
-                e.t = t
-            e.ver = ver
-        return e
+        """operand copies of `p`; re-cast inside a forward capture unless _refresh_weights() has just done it (weights.WeightCache.get)"""
+        return self.weights.get(p, need_t, force=self._capturing == "fwd" and not self._refreshed, frozen=self._capturing == "bwd")
 
     def _refresh_weights(self):
         """Bring the bf16 operand copies of every encoder weight up to date in ONE launch (pvrl_cast_weights_multi_bf16)
@@ -530,35 +503,7 @@ class EncoderEngine(GraphReplay):
             plist += [(blk.temporal_attn.qkv.weight, True), (blk.temporal_attn.proj.weight, True),
                       (blk.temporal_fc.weight, True), (blk.attn.qkv.weight, True), (blk.attn.proj.weight, True),
                       (blk.mlp.fc1.weight, True), (blk.mlp.fc2.weight, True)]
-        self.refresh_params(plist, force=self._capturing == "fwd")
-
-    def refresh_params(self, plist, force=False):
-        """operand copies of the (parameter, transposed copy wanted) pairs of `plist` in ONE launch; `force`: re-cast the current ones
-        as well (inside a forward capture: a replay must refresh the copies after an optimiser step)"""
-        todo = []
-        epoch = getattr(self.m, "weights_epoch", 0)
-        for p, need_t in plist:
-            e = self._w.get(id(p))
-            if e is None:
-                e = _W()
-                self._w[id(p)] = e
-            ver = (p._version, epoch if p.requires_grad else 0, p.data_ptr())
-            fresh = e.ver == ver and e.w is not None and e.w.device == p.device and (e.t is not None or not need_t)
-            if fresh and not force:
-                continue
-            w2 = p.detach().reshape(p.shape[0], -1)
-            if not w2.is_contiguous():
-                continue                       # left to _weight()
-            if e.w is None or e.w.device != p.device:
-                e.w = torch.empty(w2.shape, device=p.device, dtype=OP16)
-                e.t = None
-            if need_t and e.t is None:
-                e.t = torch.empty((w2.shape[1], w2.shape[0]), device=p.device, dtype=OP16)
-            todo.append((w2, e.w, e.t if need_t else None, e, ver))
-        if todo:
-            ops.cast_weights_multi([(w2, w, t) for w2, w, t, _, _ in todo])
-            for _, _, _, e, ver in todo:
-                e.ver = ver
+        self.weights.refresh(plist, force=self._capturing == "fwd")
 
     def _fused_temporal(self, blk):
         """The temporal branch applies two linear maps back to back (vit.py:131-134: temporal_attn.proj, DropPath, then
@@ -567,10 +512,7 @@ class EncoderEngine(GraphReplay):
         W_e is rebuilt from the bf16 operand copies whenever either weight changed (a 768^3 MFMA GEMM); the parameter
         gradients are recovered from dW_e in backward (`_temporal_chain_all`)."""
         wf, wp = blk.temporal_fc.weight, blk.temporal_attn.proj.weight
-        e = self._w.get(("fused_t", id(wf)))
-        if e is None:
-            e = _W()
-            self._w[("fused_t", id(wf))] = e
+        e = self.weights.entry(wf, "fused_t")
         ef, ep = self._weight(wf), self._weight(wp)
         ver = (ef.ver, ep.ver, blk.temporal_attn.proj.bias._version)
         if self._capturing == "bwd" or id(blk) in self._fused_fresh:     # (built a moment ago by _build_fused_all)
@@ -586,11 +528,11 @@ class EncoderEngine(GraphReplay):
     def _fused_temporal_stale(self, blk):
         if self._capturing == "fwd":
             return True
-        e = self._w.get(("fused_t", id(blk.temporal_fc.weight)))
+        e = self.weights.peek(blk.temporal_fc.weight, "fused_t")
         if e is None or e.w is None:
             return True
-        ef = self._w.get(id(blk.temporal_fc.weight))
-        ep = self._w.get(id(blk.temporal_attn.proj.weight))
+        ef = self.weights.peek(blk.temporal_fc.weight)
+        ep = self.weights.peek(blk.temporal_attn.proj.weight)
         return ef is None or ep is None or e.ver != (ef.ver, ep.ver, blk.temporal_attn.proj.bias._version)
 
     def _build_fused_all(self):
@@ -604,10 +546,7 @@ class EncoderEngine(GraphReplay):
         ents, probs = [], []
         for blk in stale:
             wf, wp = blk.temporal_fc.weight, blk.temporal_attn.proj.weight
-            e = self._w.get(("fused_t", id(wf)))
-            if e is None:
-                e = _W()
-                self._w[("fused_t", id(wf))] = e
+            e = self.weights.entry(wf, "fused_t")
             ef, ep = self._weight(wf), self._weight(wp)
             ents.append((blk, e, ef, ep))
             probs.append(dict(A=ef.w, W=ep.t))                              # [out, in] = W_fc [out, mid] . W_proj [mid, in]

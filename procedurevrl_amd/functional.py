@@ -38,7 +38,7 @@ class StackFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, owner, resblocks, nseq, S, causal, kpm, heads, anchor):
         from .tfm_engine import StackEngine
-        eng = StackEngine(resblocks, owner.weight_cache, owner.grad_target, heads=heads, grad_store=getattr(owner, "grad_store", None))
+        eng = StackEngine(resblocks, owner.weights.get, owner.grad_target, heads=heads, grad_store=getattr(owner, "grad_store", None))
         need = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[8])
         y, saved = eng.forward(x.contiguous(), nseq, S, causal=causal, kpm=kpm, save=need)
         ctx.eng, ctx.saved_acts, ctx.owner_ref = eng, saved, owner

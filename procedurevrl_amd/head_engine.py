@@ -51,15 +51,12 @@ class PretrainHeadEngine:
         return [p for p in list(o.head.parameters()) + list(o.order_tfm.parameters()) if p.requires_grad]
 
     def _wc(self, p):
-        """16-bit operand copies of a stack weight (the encoder engine's cache).  While the forward is being captured the
+        """16-bit operand copies of a stack weight (the model's weights.WeightCache).  While the forward is being captured the
         first use of every weight re-casts it INSIDE the graph: a replay must refresh the copies after an optimiser step."""
-        eng = self.o.engine
-        if self._cap == "fwd" and id(p) not in self._cap_seen:
+        force = self._cap == "fwd" and id(p) not in self._cap_seen
+        if force:
             self._cap_seen.add(id(p))
-            e = eng._w.get(id(p))
-            if e is not None:
-                e.ver = None
-        return eng._weight(p)
+        return self.o.weights.get(p, force=force)
 
     def draws(self, rng, b, n, dev):
         """the reference's random draws of one forward (tfm_model.py:145, 279-286, 180; vit.py:345), pinned by `rng` or fresh"""
@@ -223,14 +220,14 @@ class PretrainHeadEngine:
         return d_feat
 
     def _refresh_stack_weights(self):
-        """16-bit operand copies of the stack's 16 weight matrices in ONE launch (engine.refresh_params) instead of one per matrix on
+        """16-bit operand copies of the stack's 16 weight matrices in ONE launch (weights.WeightCache.refresh) instead of one per matrix on
         first use; inside the forward capture every copy is re-cast (a replay must refresh them after an optimiser step)"""
         ot = self.o.order_tfm
         plist = []
         for blk in ot.temporalModelling.resblocks:
             plist += [(blk.attn.in_proj_weight, True), (blk.attn.out_proj.weight, True), (blk.mlp.c_fc.weight, True),
                       (blk.mlp.c_proj.weight, True)]
-        self.o.engine.refresh_params(plist, force=self._cap == "fwd")
+        self.o.weights.refresh(plist, force=self._cap == "fwd")
         if self._cap == "fwd":
             self._cap_seen.update(id(p) for p, _ in plist)
 

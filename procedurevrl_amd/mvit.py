@@ -21,7 +21,8 @@ from . import ops
 from . import ops_mvit as om
 from ._lib import lib
 from .build import MODEL_REGISTRY
-from .engine import EncoderEngine, GradStore, GraphReplay
+from .engine import GradStore, GraphReplay
+from .weights import WeightCache
 from .vit import VisionTransformer as _StepMatchingModel, trunc_normal_
 
 OP16 = ops.OP16
@@ -210,25 +211,16 @@ class MViT_encoder(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------ engine
-class _PW:
-    """zero-padded bf16 operand copies of one weight: w [Np, Kp] (forward), t [Kp, Np] (data gradient), bias [Np] fp32"""
-    __slots__ = ("w", "t", "b", "ver", "N", "K")
-
-
 class MViTEngine(GraphReplay):
     """Kernel schedule of MViT_encoder.forward (slowfast_mvit/mvit.py:346-407) and its hand-written backward.
     Token matrices are fp32 [B*L + B, pad128(C)]: patch tokens (b, t, h, w) first, the B cls tokens last.
     The ~3,000 launches of a step are replayed from HIP graphs (engine.GraphReplay; with a data-parallel gradient hook
     installed the backward is one graph per block, the hook running between them)."""
 
-    _weight = EncoderEngine._weight      # un-padded bf16 copies for the width-512 stacks (order transformer, text tower)
-    refresh_params = EncoderEngine.refresh_params
-
     def __init__(self, owner, enc):
-        self.m = owner                   # the wrapper (weights_epoch, grad_target)
+        self.m = owner                   # the wrapper (grad_target, grad_store)
         self.enc = enc
-        self._w = {}
-        self._pw = {}
+        self.weights = owner.weights     # weights.WeightCache: the padded operand copies (and the width-512 stacks' plain ones)
         self._idx = {}
         self.saved = None
         self.grad_hook = None
@@ -265,28 +257,8 @@ class MViTEngine(GraphReplay):
 
     # -------------------------------------------------------------- weights
     def _wpad(self, weight, bias=None, Np=None, Kp=None):
-        e = self._pw.get(id(weight))
-        ver = (weight._version, bias._version if bias is not None else -1, getattr(self.m, "weights_epoch", 0),
-               weight.data_ptr())
-        if self._capturing == "bwd":      # the forward graph of the same step refreshed the padded copies
-            assert e is not None
-            return e
-        if self._capturing == "fwd" or e is None or e.ver != ver or e.w.device != weight.device:
-            w2 = weight.detach().reshape(weight.shape[0], -1).contiguous()
-            N, K = w2.shape
-            Np = om.pad128(N) if Np is None else Np
-            Kp = om.pad128(K) if Kp is None else Kp
-            if e is None or e.w.device != weight.device or tuple(e.w.shape) != (Np, Kp):
-                e = _PW()
-                e.w = torch.zeros((Np, Kp), device=weight.device, dtype=OP16)
-                e.t = torch.zeros((Kp, Np), device=weight.device, dtype=OP16)
-                e.b = torch.zeros(Np, device=weight.device, dtype=F32)
-                self._pw[id(weight)] = e
-            lib().call("pvrl_cast_weight_pad_bf16", ops._ptr(w2), ops._ptr(e.w), Kp, ops._ptr(e.t), Np, N, K,
-                       ops._ptr(bias.detach()) if bias is not None else None, ops._ptr(e.b) if bias is not None else None,
-                       ops._stream())
-            e.N, e.K, e.ver = N, K, ver
-        return e
+        """zero-padded operand copies; re-cast by every use inside a forward capture (weights.WeightCache.padded)"""
+        return self.weights.padded(weight, bias, Np, Kp, force=self._capturing == "fwd", frozen=self._capturing == "bwd")
 
     def _rel_idx(self, i, blk, q_thw, k_thw, dev):
         c = self._idx.get(i)
@@ -599,8 +571,8 @@ class VisionTransformer(_StepMatchingModel):
         self.num_features = self.embed_dim = embed_dim
         self.ln_eps = 1e-6
         self._init_heads(embed_dim, label_emb, mlp, text_model, num_seg, num_classes, cfg)
+        self.weights = WeightCache(self)
         self.engine = MViTEngine(self, self.video_encoder)
-        self.weight_cache = self.engine._weight
         self._grad_store = None
         self._label_cache = None
         if hasattr(self, "order_tfm"):

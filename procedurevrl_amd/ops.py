@@ -617,6 +617,16 @@ def cast_weight(w, out=None, out_t=None, need_t=True):
     return out, (out_t if need_t else None)
 
 
+def cast_weight_pad(w, out, out_t, bias=None, out_b=None):
+    """fp32 [N, K] -> the top-left corners of bf16 `out` [Np, Kp] and `out_t` [Kp, Np]; bias fp32 [N] -> the head of `out_b` [Np]"""
+    (N, K), (Np, Kp) = w.shape, out.shape
+    assert w.dtype == F32 and w.is_contiguous() and Np >= N and Kp >= K and out.dtype == OP16 and out.is_contiguous()
+    assert out_t.shape == (Kp, Np) and out_t.dtype == OP16 and out_t.is_contiguous()
+    assert bias is None or (bias.dtype == F32 and bias.numel() == N and out_b.dtype == F32 and out_b.numel() >= N)
+    lib().call("pvrl_cast_weight_pad_bf16", _ptr(w), _ptr(out), Kp, _ptr(out_t), Np, N, K,
+               _ptr(bias.detach()) if bias is not None else None, _ptr(out_b) if bias is not None else None, _stream())
+
+
 def gemv_rows(W, x, out=None, beta=0.0, gscale=None):
     """out[r] = beta * out[r] + gscale * W[r, :] . x  (W fp32 or bf16 [R, C] row-major, x fp32 [C]) -> fp32 [R]"""
     _chk2d(W)

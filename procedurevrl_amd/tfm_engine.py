@@ -24,7 +24,8 @@ LN_EPS = 1e-5
 
 class StackEngine:
     """Runs a list of residual attention blocks (objects with ln_1, attn.in_proj_weight/bias,
-    attn.out_proj, ln_2, mlp.c_fc, mlp.c_proj).  Shares the weight-copy cache of `enc` (EncoderEngine)."""
+    attn.out_proj, ln_2, mlp.c_fc, mlp.c_proj).  `weight_cache(p)` -> the 16-bit operand copies `.w` / `.t` of weight `p`:
+    the model's weights.WeightCache.get, or a caller's wrapper of it that adds a capture policy (head_engine)."""
 
     def __init__(self, resblocks, weight_cache, grad_target=None, heads=8, grad_store=None):
         """`grad_store` (optional callable -> engine.GradStore): parameter gradients are then written in "fused" form -- the kernels

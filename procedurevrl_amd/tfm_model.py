@@ -274,7 +274,7 @@ class ClipTextModel(nn.Module):
         own = self._owner[0]
         n, S = text.shape
         x = self.token_embedding.weight[text] + self.positional_embedding[None, :S]
-        eng = StackEngine(self.transformer.resblocks, own.weight_cache, None, heads=self.transformer.heads)
+        eng = StackEngine(self.transformer.resblocks, own.weights.get, None, heads=self.transformer.heads)
         y, _ = eng.forward(x.reshape(n * S, -1).contiguous().float(), n, S, causal=True, save=False)
         eot = text.argmax(dim=-1) + torch.arange(n, device=text.device) * S
         pooled = y[eot].contiguous()

@@ -20,6 +20,7 @@ from .build import MODEL_REGISTRY
 from .engine import EncoderEngine, GradStore
 from .functional import EncoderFn, kl_topk_loss, l2norm, linear_f32, mse_loss, step_logits
 from .head_engine import PretrainHeadEngine, PretrainHeadFn
+from .weights import WeightCache
 from .tfm_model import ClipTextModel, DiffusionTransformer as OrderTransformer
 
 
@@ -120,8 +121,8 @@ class VisionTransformer(nn.Module):
                 nn.init.constant_(blk.temporal_fc.weight, 0)
                 nn.init.constant_(blk.temporal_fc.bias, 0)
 
+        self.weights = WeightCache(self)       # 16-bit operand copies of the master weights, current as of `weights_epoch`
         self.engine = EncoderEngine(self)
-        self.weight_cache = self.engine._weight
         self._grad_store = None
         self._label_cache = None
         if hasattr(self, "order_tfm"):

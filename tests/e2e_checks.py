@@ -709,6 +709,85 @@ def check_hip_graph_replay():
     return out
 
 
-ALL_CHECKS = [check_pretrain_head_engine, check_step_is_bit_reproducible, check_hip_graph_replay, check_decoded_clips_train_step, check_block_golden, check_e2e_golden, check_train_step_small, check_train_step_droppath_ragged, check_train_step_last_block_unpruned, check_train_step_fp32_residual_stream, check_train_step_undefined_rows_nan_filled,
+def replay_after_optimizer_step(tag, model, cfg, step, engines):
+    """A graph replay after a FusedOptimizer step reads current 16-bit weight copies.  The fused optimiser updates the weights through
+    its flat buffer and advances `weights_epoch`, no `_version` changes: only the casts captured INSIDE the forward graphs can bring
+    the copies up to date.  `step()` -> (logits, gradients as one tensor or a dict of tensors) runs one training step on a fixed
+    input with every `.grad` reset to None first; `engines`: everything with `use_graphs` / `_graphs` / `_gseen` on the step's path.
+    Capture (GRAPH_WARMUP + 1 steps), one optimiser step, replay: bit-equal to the eager launches (`use_graphs` off) of the same model
+    on the same input, and different from the logits before the optimiser step (a replay on stale copies would repeat those).
+    Shared with mvit_checks.check_mvit_replay_after_optimizer_step."""
+    from procedurevrl_amd.optimizer import construct_optimizer, set_lr
+    cfg.SOLVER.OPTIMIZING_METHOD = "adamw"
+    opt = construct_optimizer(model, cfg)
+    set_lr(opt, 1e-3)
+
+    def differ(a, b):
+        if isinstance(a, dict):
+            return float(set(a) != set(b)) + float(sum(int((a[k] != b[k]).sum()) for k in a if k in b))
+        return float((a != b).sum())
+
+    def optimizer_step():
+        model.model.adopt_grads()
+        opt.step()
+
+    # the first optimiser step moves the parameters into its flat buffer: new data_ptr()s, i.e. new graph keys -- before any capture
+    step()
+    optimizer_step()
+    for _ in range(max(e.GRAPH_WARMUP for e in engines) + 1):
+        pre = step()
+    out = [(f"{tag}: graphs were captured (0 = yes)", 0.0 if all(len(e._graphs) == 1 for e in engines) else 1.0, 0.0)]
+    seen = [dict(e._gseen) for e in engines]
+    optimizer_step()
+    rep = step()
+    out.append((f"{tag}: the step after the optimiser step was a replay (0 = yes)",
+                0.0 if all(len(e._graphs) == 1 and e._gseen == s and e.use_graphs for e, s in zip(engines, seen)) else 1.0, 0.0))
+    for e in engines:
+        e.use_graphs = False
+    eager = step()
+    out += [(f"{tag}: replay after an optimiser step, logits differ from eager (count)", differ(rep[0], eager[0]), 0.0),
+            (f"{tag}: replay after an optimiser step, gradients differ from eager (count)", differ(rep[1], eager[1]), 0.0),
+            (f"{tag}: replay after an optimiser step repeats the logits from before it (0 = they differ)",
+             0.0 if differ(rep[0], pre[0]) > 0 else 1.0, 0.0)]
+    return out
+
+
+def check_replay_after_optimizer_step():
+    """`replay_after_optimizer_step` on the TimeSformer encoder step (5 clips of 8 x 48 x 48, 2 blocks: the engine's bulk refresh and
+    its fused temporal maps) and on the full pre-training step of tests/golden/e2e.pt with every draw pinned (encoder, frozen text
+    tower, PretrainHeadEngine: the head's forward capture re-casts the order transformer's weights inside its own graph)."""
+    from procedurevrl_amd.datasets import synthetic_label_emb
+    from procedurevrl_amd.functional import kl_topk_loss
+    cfg = make_cfg(2, 48, 200, drop_path=0.0)
+    model = build(cfg, synthetic_label_emb(200, 512, seed=1)).to(DEV).train()
+    with torch.no_grad():
+        for blk in model.model.blocks:
+            torch.nn.init.normal_(blk.temporal_fc.weight, std=0.02)
+    g = torch.Generator().manual_seed(4)
+    x = torch.randn(5, 3, 8, 48, 48, generator=g).to(DEV)
+    teacher = (torch.randn(5, 200, generator=g) * 3).to(DEV)
+
+    def step():
+        model.zero_grad(set_to_none=True)
+        pred = model(x)
+        kl_topk_loss(pred, teacher, 5).backward()
+        return pred.detach().clone(), model.model.adopt_grads().flat.clone()
+
+    out = replay_after_optimizer_step("encoder", model, cfg, step, [model.model.engine])
+
+    f = load("e2e")
+    cfg, model, full = _e2e_model(f)
+    model.train()
+    vt = model.model
+    _e2e_step(model, cfg, f)            # creates the head engine
+
+    def step():
+        r = _e2e_step(model, cfg, f)
+        return r["pred"], r["grads"]
+
+    return out + replay_after_optimizer_step("pre-training", model, cfg, step, [vt.engine, vt.head_engine])
+
+
+ALL_CHECKS = [check_pretrain_head_engine, check_step_is_bit_reproducible, check_hip_graph_replay, check_replay_after_optimizer_step, check_decoded_clips_train_step, check_block_golden, check_e2e_golden, check_train_step_small, check_train_step_droppath_ragged, check_train_step_last_block_unpruned, check_train_step_fp32_residual_stream, check_train_step_undefined_rows_nan_filled,
               check_train_step_t4, check_train_step_t32, check_train_step_crop256, check_forecast_eval_golden, check_embed_resize_golden, check_full_size,
               check_train_step_t32_full_res, check_text_tower_full_size, check_timed_config_train_step, check_bench_config_two_clips]

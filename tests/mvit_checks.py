@@ -475,6 +475,31 @@ def check_mvit_hip_graph_replay():
     return out
 
 
+def check_mvit_replay_after_optimizer_step():
+    """e2e_checks.replay_after_optimizer_step on the MViT encoder step (the small geometry of check_mvit_hip_graph_replay): the padded
+    operand copies are re-cast inside the forward graph, so a replay after a fused optimiser step computes on the new weights."""
+    from e2e_checks import replay_after_optimizer_step
+    from procedurevrl_amd.build import build_model
+    from procedurevrl_amd.datasets import synthetic_label_emb
+    from procedurevrl_amd.functional import kl_topk_loss
+    g = _load("mvit_small")
+    cfg = _mvit_cfg(g["mvit"], 4, 64, K=128)
+    cfg.TRAIN.LABEL_EMB = synthetic_label_emb(128, 512, seed=1)
+    torch.manual_seed(0)
+    model = build_model(cfg, gpu_id=0).train()
+    gen = torch.Generator().manual_seed(6)
+    x = torch.randn(3, 3, 4, 64, 64, generator=gen).to(DEV)
+    teacher = (torch.randn(3, 128, generator=gen) * 3).to(DEV)
+
+    def step():
+        model.zero_grad(set_to_none=True)
+        pred = model(x)
+        kl_topk_loss(pred, teacher, 5).backward()
+        return pred.detach().clone(), model.model.adopt_grads().flat.clone()
+
+    return replay_after_optimizer_step("mvit", model, cfg, step, [model.model.engine])
+
+
 def check_mvit_s_full_size_step_vs_oracle():
     """MViTv2-S at BASELINE config-5 size (16 x 224^2, 16 blocks): one clip's features AND parameter gradients of the HIP
     path against the CPU oracle (pinned to the reference by the golden tests) -- the 25,089-query / 1,569-key attention
@@ -602,4 +627,4 @@ TIMED_GRAD_OBS = ({"patch_embed.proj.weight": 2.12e-2, "blocks.0.attn.qkv.weight
                    "blocks.1.attn.rel_pos_t": 4.73e-2, "blocks.3.attn.pool_k.weight": 1.6e-2, "blocks.7.mlp.fc1.weight": 9.3e-3,
                    "blocks.14.attn.qkv.bias": 5.2e-3, "blocks.15.mlp.fc2.weight": 7.2e-3, "norm.weight": 6.0e-3, "cls_token": 1.01e-2})
 
-ALL_CHECKS = [check_mvit_timed_config_train_step, check_mvit_s_full_size_step_vs_oracle, check_mvit_hip_graph_replay, check_mvit_encoder_small_golden, check_mvit_droppath_golden, check_mvit_e2e_golden, check_mvit_pretrain_steps, check_mvit_s_features, check_mvit_im2col_ln, check_mvit_pool, check_mvit_maxpool_rel, check_mvit_attention]
+ALL_CHECKS = [check_mvit_timed_config_train_step, check_mvit_s_full_size_step_vs_oracle, check_mvit_hip_graph_replay, check_mvit_replay_after_optimizer_step, check_mvit_encoder_small_golden, check_mvit_droppath_golden, check_mvit_e2e_golden, check_mvit_pretrain_steps, check_mvit_s_features, check_mvit_im2col_ln, check_mvit_pool, check_mvit_maxpool_rel, check_mvit_attention]
