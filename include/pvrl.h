@@ -230,6 +230,16 @@ int pvrl_frames_u8_patchify(const void* frames, const int32_t* params, int64_t B
 /* The same input pipeline producing the fp32 clip tensor [B,3,T,crop,crop] of the reference's loader (MViT stem input). */
 int pvrl_frames_u8_to_f32(const void* frames, const int32_t* params, int64_t B, int64_t T, int64_t H0, int64_t W0,
                           int64_t crop, const float* mean3, const float* std3, float* out, void* stream);
+/* Both of the above with SHARED source slabs: frames uint8 [S,T,H0,W0,3], src int32 [B] (device, 0 <= src[b] < S: the caller
+ * checks it on the host, the kernels do not), output clip b = params[b] applied to slab src[b] -- the three spatial crops of a
+ * test view (lib/datasets/epickitchens.py:124-135) from ONE decoded copy.  Same arithmetic, operation for operation: bit-equal to
+ * the plain entry points on frames[src] replicated. */
+int pvrl_frames_u8_patchify_views(const void* frames, const int32_t* params, const int32_t* src, int64_t S, int64_t B,
+                                  int64_t T, int64_t H0, int64_t W0, int64_t crop, const float* mean3, const float* std3,
+                                  void* out, int64_t ldo, void* stream);
+int pvrl_frames_u8_to_f32_views(const void* frames, const int32_t* params, const int32_t* src, int64_t S, int64_t B, int64_t T,
+                                int64_t H0, int64_t W0, int64_t crop, const float* mean3, const float* std3, float* out,
+                                void* stream);
 /* E[n*T+t] = bias + pos_embed[1+n] + time_embed[t]  (vit.py:370-407), and its batch-summed gradient. */
 int pvrl_embed_table(const float* pos, const float* time, const float* bias, float* E, int64_t N, int64_t T, int64_t C,
                      void* stream);
@@ -315,6 +325,18 @@ int pvrl_mix_clips(float* x, const pvrl_mix_desc* desc, int64_t B, int64_t C, in
 int pvrl_soft_ce(const float* x, int64_t ldx, int64_t rows, int64_t K, const float* target, int64_t ldt,
                  const int64_t* labels, const pvrl_mix_desc* desc, float on, float off, float grad_scale, float* row_loss,
                  float* dx, int64_t ldd, void* stream);
+
+/* Multi-view test ensemble (lib/utils/meters.py `EPICTestMeter.update_stats` :1040-1047, `TestMeter.update_stats` :103-128):
+ * for ind = 0..N-1 IN ORDER, vid = clip_ids[ind] / num_clips:
+ *     video_labels[vid] = labels[ind];  video_preds[vid] += preds[ind]  (mode 1: elementwise max, NaN wins as in torch.max);
+ *     clip_count[vid] += 1  (clip_count may be null).
+ * preds fp32 [N, C] (ldp), video_preds fp32 [V, C] (ldv), ids / labels / counts int64, all on the device.  No atomics: one
+ * workgroup per video present in the batch folds that video's rows in increasing ind, so the fp32 result is bit-equal to the
+ * reference's Python loop.  A clip id outside [0, V * num_clips) contributes nothing and sets *bad (int32, device) to 1; *bad is
+ * never cleared here.  No host sync, no allocation; N == 0 launches nothing. */
+int pvrl_view_ensemble(const float* preds, int64_t ldp, const int64_t* clip_ids, const int64_t* labels, int64_t N, int64_t C,
+                       int64_t num_clips, int mode, float* video_preds, int64_t ldv, int64_t V, int64_t* video_labels,
+                       int64_t* clip_count, int32_t* bad, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * RandAugment of decoded uint8 clips (lib/datasets/autoaugment.py `rand_augment_transform`, applied per frame through PIL at

@@ -42,11 +42,14 @@ __global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__
 // frames uint8 [B][T][H0][W0][3] (decoder order) ; prm int32 [B][5] = {new_h, new_w, y_off, x_off, flip}
 //   ->  out bf16 [(b, n, t)][c*256 + py*16 + px] of the (crop x crop) clip, normalised (v/255 - mean)/std.
 // One thread = 8 consecutive output pixels of one row, all 3 channels (interleaved source bytes are read once).
+// VIEWS: output clip b reads source slab src[b] of frames [S][T][H0][W0][3] (several crops of one decoded view,
+// pvrl_frames_u8_patchify_views) instead of slab b; everything else is the same code, so the two agree bit for bit.
+template <bool VIEWS>
 __global__ __launch_bounds__(256) void frames_u8_patchify_kernel(const unsigned char* __restrict__ frames,
-                                                                 const int* __restrict__ prm, op_t* __restrict__ out,
-                                                                 int B, int T, int H0, int W0, int crop, float m0,
-                                                                 float m1, float m2, float s0, float s1, float s2,
-                                                                 long ldo) {
+                                                                 const int* __restrict__ prm, const int* __restrict__ src,
+                                                                 op_t* __restrict__ out, int B, int T, int H0, int W0,
+                                                                 int crop, float m0, float m1, float m2, float s0,
+                                                                 float s1, float s2, long ldo) {
   const int xg = crop >> 3, PW = crop >> 4;
   const long total = (long)B * T * crop * xg;
   const float mean[3] = {m0, m1, m2}, istd[3] = {1.f / s0, 1.f / s1, 1.f / s2};
@@ -63,8 +66,9 @@ __global__ __launch_bounds__(256) void frames_u8_patchify_kernel(const unsigned 
     fy = fy < 0.f ? 0.f : fy;
     const int y0 = (int)fy, y1 = y0 + (y0 < H0 - 1 ? 1 : 0);
     const float ly1 = fy - (float)y0, ly0 = 1.f - ly1;
-    const unsigned char* f0 = frames + (((long)b * T + t) * H0 + y0) * W0 * 3;
-    const unsigned char* f1 = frames + (((long)b * T + t) * H0 + y1) * W0 * 3;
+    const int sb = VIEWS ? src[b] : b;
+    const unsigned char* f0 = frames + (((long)sb * T + t) * H0 + y0) * W0 * 3;
+    const unsigned char* f1 = frames + (((long)sb * T + t) * H0 + y1) * W0 * 3;
     opx8 o[3];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -91,10 +95,13 @@ __global__ __launch_bounds__(256) void frames_u8_patchify_kernel(const unsigned 
 
 // Same input pipeline, producing the fp32 clip tensor [B][3][T][crop][crop] the reference's loader would have shipped
 // (for consumers that do their own im2col, e.g. the MViT stem).  One thread = 4 consecutive output pixels of one channel row.
+// VIEWS as above (pvrl_frames_u8_to_f32_views).
+template <bool VIEWS>
 __global__ __launch_bounds__(256) void frames_u8_to_f32_kernel(const unsigned char* __restrict__ frames,
-                                                               const int* __restrict__ prm, float* __restrict__ out, int B,
-                                                               int T, int H0, int W0, int crop, float m0, float m1,
-                                                               float m2, float s0, float s1, float s2) {
+                                                               const int* __restrict__ prm, const int* __restrict__ src,
+                                                               float* __restrict__ out, int B, int T, int H0, int W0,
+                                                               int crop, float m0, float m1, float m2, float s0, float s1,
+                                                               float s2) {
   const int xg = crop >> 2;
   const long total = (long)B * 3 * T * crop * xg;
   const float mean[3] = {m0, m1, m2}, istd[3] = {1.f / s0, 1.f / s1, 1.f / s2};
@@ -112,8 +119,9 @@ __global__ __launch_bounds__(256) void frames_u8_to_f32_kernel(const unsigned ch
     fy = fy < 0.f ? 0.f : fy;
     const int y0 = (int)fy, y1 = y0 + (y0 < H0 - 1 ? 1 : 0);
     const float ly1 = fy - (float)y0, ly0 = 1.f - ly1;
-    const unsigned char* f0 = frames + (((long)b * T + t) * H0 + y0) * W0 * 3 + c;
-    const unsigned char* f1 = frames + (((long)b * T + t) * H0 + y1) * W0 * 3 + c;
+    const int sb = VIEWS ? src[b] : b;
+    const unsigned char* f0 = frames + (((long)sb * T + t) * H0 + y0) * W0 * 3 + c;
+    const unsigned char* f1 = frames + (((long)sb * T + t) * H0 + y1) * W0 * 3 + c;
     f32x4 o;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -380,33 +388,61 @@ extern "C" int pvrl_patchify(const float* frames, int64_t B, int64_t T, int64_t 
   return PVRL_OK;
 }
 
-extern "C" int pvrl_frames_u8_patchify(const void* frames, const int32_t* params, int64_t B, int64_t T, int64_t H0,
-                                       int64_t W0, int64_t crop, const float* mean3, const float* std3, void* out,
-                                       int64_t ldo, void* stream) {
+// shared launcher of pvrl_frames_u8_patchify (src == nullptr: clip b reads slab b) and its _views form
+static int launch_frames_u8_patchify(const void* frames, const int32_t* params, const int32_t* src, int64_t B, int64_t T,
+                                     int64_t H0, int64_t W0, int64_t crop, const float* mean3, const float* std3, void* out,
+                                     int64_t ldo, void* stream) {
   if (B <= 0) return PVRL_OK;
   if (!frames || !params || !mean3 || !std3 || !out || crop <= 0 || (crop % 16) || (ldo % 8) || ldo < 768 || H0 <= 0 ||
       W0 <= 0)
     return PVRL_EINVAL;
   if (std3[0] == 0.f || std3[1] == 0.f || std3[2] == 0.f) return PVRL_EINVAL;
   const long total = B * T * crop * (crop >> 3);
-  hipLaunchKernelGGL(frames_u8_patchify_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
-                     (const unsigned char*)frames, (const int*)params, (op_t*)out, (int)B, (int)T, (int)H0, (int)W0,
-                     (int)crop, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], (long)ldo);
+  hipLaunchKernelGGL(src ? frames_u8_patchify_kernel<true> : frames_u8_patchify_kernel<false>, dim3(grid_for(total)),
+                     dim3(256), 0, (hipStream_t)stream, (const unsigned char*)frames, (const int*)params, (const int*)src,
+                     (op_t*)out, (int)B, (int)T, (int)H0, (int)W0, (int)crop, mean3[0], mean3[1], mean3[2], std3[0],
+                     std3[1], std3[2], (long)ldo);
+  PVRL_LAUNCH_CHECK();
+  return PVRL_OK;
+}
+
+extern "C" int pvrl_frames_u8_patchify(const void* frames, const int32_t* params, int64_t B, int64_t T, int64_t H0,
+                                       int64_t W0, int64_t crop, const float* mean3, const float* std3, void* out,
+                                       int64_t ldo, void* stream) {
+  return launch_frames_u8_patchify(frames, params, nullptr, B, T, H0, W0, crop, mean3, std3, out, ldo, stream);
+}
+
+extern "C" int pvrl_frames_u8_patchify_views(const void* frames, const int32_t* params, const int32_t* src, int64_t S,
+                                             int64_t B, int64_t T, int64_t H0, int64_t W0, int64_t crop,
+                                             const float* mean3, const float* std3, void* out, int64_t ldo, void* stream) {
+  if (B > 0 && (!src || S <= 0)) return PVRL_EINVAL;
+  return launch_frames_u8_patchify(frames, params, src, B, T, H0, W0, crop, mean3, std3, out, ldo, stream);
+}
+
+static int launch_frames_u8_to_f32(const void* frames, const int32_t* params, const int32_t* src, int64_t B, int64_t T,
+                                   int64_t H0, int64_t W0, int64_t crop, const float* mean3, const float* std3, float* out,
+                                   void* stream) {
+  if (B <= 0) return PVRL_OK;
+  if (!frames || !params || !mean3 || !std3 || !out || crop <= 0 || (crop % 4) || H0 <= 0 || W0 <= 0) return PVRL_EINVAL;
+  if (std3[0] == 0.f || std3[1] == 0.f || std3[2] == 0.f) return PVRL_EINVAL;
+  const long total = B * 3 * T * crop * (crop >> 2);
+  hipLaunchKernelGGL(src ? frames_u8_to_f32_kernel<true> : frames_u8_to_f32_kernel<false>, dim3(grid_for(total)), dim3(256),
+                     0, (hipStream_t)stream, (const unsigned char*)frames, (const int*)params, (const int*)src, out, (int)B,
+                     (int)T, (int)H0, (int)W0, (int)crop, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
   PVRL_LAUNCH_CHECK();
   return PVRL_OK;
 }
 
 extern "C" int pvrl_frames_u8_to_f32(const void* frames, const int32_t* params, int64_t B, int64_t T, int64_t H0, int64_t W0,
                                      int64_t crop, const float* mean3, const float* std3, float* out, void* stream) {
-  if (B <= 0) return PVRL_OK;
-  if (!frames || !params || !mean3 || !std3 || !out || crop <= 0 || (crop % 4) || H0 <= 0 || W0 <= 0) return PVRL_EINVAL;
-  if (std3[0] == 0.f || std3[1] == 0.f || std3[2] == 0.f) return PVRL_EINVAL;
-  const long total = B * 3 * T * crop * (crop >> 2);
-  hipLaunchKernelGGL(frames_u8_to_f32_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
-                     (const unsigned char*)frames, (const int*)params, out, (int)B, (int)T, (int)H0, (int)W0, (int)crop,
-                     mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
-  PVRL_LAUNCH_CHECK();
-  return PVRL_OK;
+  return launch_frames_u8_to_f32(frames, params, nullptr, B, T, H0, W0, crop, mean3, std3, out, stream);
+}
+
+extern "C" int pvrl_frames_u8_to_f32_views(const void* frames, const int32_t* params, const int32_t* src, int64_t S,
+                                           int64_t B, int64_t T, int64_t H0, int64_t W0, int64_t crop, const float* mean3,
+                                           const float* std3, float* out, void* stream) {
+  if (B > 0 && (!src || S <= 0)) return PVRL_EINVAL;
+  return launch_frames_u8_to_f32(frames, params, src, B, T, H0, W0, crop, mean3, std3, out, stream);
 }
 
 extern "C" int pvrl_embed_table(const float* pos, const float* time, const float* bias, float* E, int64_t N, int64_t T,

@@ -55,7 +55,9 @@ class SyntheticHowTo100M(torch.utils.data.Dataset):
 class SyntheticTestClips(torch.utils.data.Dataset):
     """Multi-view test split: entry `i` is view `i % num_clips` of video `i // num_clips` (the reference's test
     datasets index clips that way; `TestMeter.update_stats` recovers the video as `clip_id // num_clips`,
-    lib/utils/meters.py:104-131).  Frames of one video share a per-video pattern so the ensemble is meaningful."""
+    lib/utils/meters.py:104-131).  Frames of one video share a per-video pattern so the ensemble is meaningful.
+    Under TEST.DATASET "Epickitchens" the label is the reference's {"verb", "noun"} dict (97 / 300 classes), fixed per video, and
+    the metadata carries a narration id per video (lib/datasets/epickitchens.py:205-208)."""
 
     def __init__(self, cfg, num_videos=8, seed=0):
         self.cfg = cfg
@@ -74,6 +76,9 @@ class SyntheticTestClips(torch.utils.data.Dataset):
         g = torch.Generator().manual_seed(self.seed * 100003 + 31 * index + 1)
         frames = base + 0.5 * torch.randn(3, T, S, S, generator=g)
         label = int(torch.randint(0, max(1, int(self.cfg.MODEL.NUM_CLASSES)), (1,), generator=gv))
+        if self.cfg.TEST.DATASET == "Epickitchens":
+            label = {"verb": torch.randint(0, 97, (1,), generator=gv)[0], "noun": torch.randint(0, 300, (1,), generator=gv)[0]}
+            return frames, label, torch.tensor(index), {"narration_id": "P01_{}".format(vid)}
         return frames, torch.tensor(label), torch.tensor(index), {}
 
 

@@ -59,6 +59,17 @@ def all_gather(tensors):
     return out
 
 
+def all_gather_unaligned(obj):
+    """distributed.py:245-281: any picklable object from every rank -> list with one entry per rank, in rank order (the
+    reference serialises into padded byte tensors over a gloo group; `all_gather_object` does the same)."""
+    world = get_world_size()
+    if world == 1:
+        return [obj]
+    out = [None] * world
+    dist.all_gather_object(out, obj)
+    return out
+
+
 def all_reduce(tensors, average=True):
     """distributed.py:53-69 (in place, sum then optional 1/world)."""
     for t in tensors:

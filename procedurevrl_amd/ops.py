@@ -522,44 +522,88 @@ def patchify(frames, out=None):
     return out
 
 
+def _check_decoded(clips):
+    """host-side validation of a transform.DecodedClips / DecodedViews before a launch (from the host copies: nothing is read
+    back) -> (B output clips, device `src` or None)"""
+    fr = clips.frames
+    ph = clips.params_host
+    if bool(((ph[:, 0] - ph[:, 2]) < clips.crop).any()) or bool(((ph[:, 1] - ph[:, 3]) < clips.crop).any()) or bool((ph[:, 2:4] < 0).any()):
+        raise ValueError("crop window leaves the rescaled frame")
+    sh = getattr(clips, "src_host", None)
+    if sh is not None:
+        if sh.shape[0] != ph.shape[0]:
+            raise ValueError(f"{sh.shape[0]} source indices for {ph.shape[0]} clips")
+        if sh.numel() and (int(sh.min()) < 0 or int(sh.max()) >= fr.shape[0]):
+            raise ValueError(f"source slab index outside [0, {fr.shape[0]})")
+    assert fr.is_cuda and fr.dtype == torch.uint8 and fr.is_contiguous()
+    return (fr.shape[0], None) if sh is None else (sh.shape[0], clips.src)
+
+
 def frames_u8_patchify(clips, out=None):
     """transform.DecodedClips (uint8 [B,T,H0,W0,3] + per-clip draws) -> bf16 [(b,n,t), 768] of the normalised,
-    rescaled, cropped, flipped clip (the reference's CPU-worker chain, fused into the im2col)."""
+    rescaled, cropped, flipped clip (the reference's CPU-worker chain, fused into the im2col).  A transform.DecodedViews
+    (B clips naming S shared source slabs) goes to the `_views` entry point: same arithmetic, same bits."""
     import ctypes
     L = lib()
     fr = clips.frames
-    assert fr.is_cuda and fr.dtype == torch.uint8 and fr.is_contiguous()
-    B, T, H0, W0, _ = fr.shape
+    B, src = _check_decoded(clips)
+    S, T, H0, W0, _ = fr.shape
     crop = clips.crop
-    ph = clips.params_host
-    if bool(((ph[:, 0] - ph[:, 2]) < crop).any()) or bool(((ph[:, 1] - ph[:, 3]) < crop).any()) or bool((ph[:, 2:4] < 0).any()):
-        raise ValueError("crop window leaves the rescaled frame")
     rows = B * (crop // 16) * (crop // 16) * T
     if out is None:
         out = torch.empty((rows, 768), device=fr.device, dtype=OP16)
     mean = (ctypes.c_float * 3)(*clips.mean)
     std = (ctypes.c_float * 3)(*clips.std)
-    L.call("pvrl_frames_u8_patchify", _ptr(fr), _ptr(clips.params), B, T, H0, W0, crop,
-           ctypes.cast(mean, ctypes.c_void_p), ctypes.cast(std, ctypes.c_void_p), _ptr(out), _ld(out), _stream())
+    tail = (B, T, H0, W0, crop, ctypes.cast(mean, ctypes.c_void_p), ctypes.cast(std, ctypes.c_void_p), _ptr(out), _ld(out), _stream())
+    if src is None:
+        L.call("pvrl_frames_u8_patchify", _ptr(fr), _ptr(clips.params), *tail)
+    else:
+        L.call("pvrl_frames_u8_patchify_views", _ptr(fr), _ptr(clips.params), _ptr(src), S, *tail)
     return out
 
 
 def frames_u8_to_f32(clips):
-    """transform.DecodedClips -> fp32 [B, 3, T, crop, crop]: the tensor the reference's CPU workers would have produced"""
+    """transform.DecodedClips (or DecodedViews) -> fp32 [B, 3, T, crop, crop]: the tensor the reference's CPU workers would
+    have produced"""
     import ctypes
     L = lib()
     fr = clips.frames
-    B, T, H0, W0, _ = fr.shape
+    B, src = _check_decoded(clips)
+    S, T, H0, W0, _ = fr.shape
     crop = clips.crop
-    ph = clips.params_host
-    if bool(((ph[:, 0] - ph[:, 2]) < crop).any()) or bool(((ph[:, 1] - ph[:, 3]) < crop).any()) or bool((ph[:, 2:4] < 0).any()):
-        raise ValueError("crop window leaves the rescaled frame")
     out = torch.empty((B, 3, T, crop, crop), device=fr.device, dtype=F32)
     mean = (ctypes.c_float * 3)(*clips.mean)
     std = (ctypes.c_float * 3)(*clips.std)
-    L.call("pvrl_frames_u8_to_f32", _ptr(fr), _ptr(clips.params), B, T, H0, W0, crop, ctypes.cast(mean, ctypes.c_void_p),
-           ctypes.cast(std, ctypes.c_void_p), _ptr(out), _stream())
+    tail = (B, T, H0, W0, crop, ctypes.cast(mean, ctypes.c_void_p), ctypes.cast(std, ctypes.c_void_p), _ptr(out), _stream())
+    if src is None:
+        L.call("pvrl_frames_u8_to_f32", _ptr(fr), _ptr(clips.params), *tail)
+    else:
+        L.call("pvrl_frames_u8_to_f32_views", _ptr(fr), _ptr(clips.params), _ptr(src), S, *tail)
     return out
+
+
+def view_ensemble(preds, clip_ids, labels, num_clips, video_preds, video_labels, clip_count, bad, mode="sum"):
+    """One batch of the multi-view test ensemble, in place on the device accumulators (lib/utils/meters.py:1040-1047; :103-128
+    for `mode="max"`): for every row in order, video = clip_id // num_clips, the label is stored, the row is added (or maxed)
+    into the video's predictions and the video's count goes up -- bit-equal to the reference's loop, no atomics, no host sync.
+    preds fp32 [N, C]; clip_ids, labels int64 [N]; video_preds fp32 [V, C]; video_labels, clip_count (or None) int64 [V];
+    bad int32 [1], set to 1 when a clip id lies outside [0, V * num_clips) (such a row contributes nothing)."""
+    if mode not in ("sum", "max"):
+        raise ValueError(f"ensemble mode {mode!r}: expected 'sum' or 'max'")
+    N, C = preds.shape
+    V = video_preds.shape[0]
+    ok = (preds.is_cuda and preds.dtype == F32 and preds.stride(1) == 1 and video_preds.dtype == F32 and video_preds.stride(1) == 1
+          and video_preds.shape[1] == C and clip_ids.dtype == torch.int64 and labels.dtype == torch.int64
+          and clip_ids.is_contiguous() and labels.is_contiguous() and clip_ids.numel() == N and labels.numel() == N
+          and video_labels.dtype == torch.int64 and video_labels.is_contiguous() and video_labels.numel() == V
+          and (clip_count is None or (clip_count.dtype == torch.int64 and clip_count.is_contiguous() and clip_count.numel() == V))
+          and bad.dtype == torch.int32 and bad.numel() >= 1
+          and all(t is None or t.device == preds.device for t in (clip_ids, labels, video_preds, video_labels, clip_count, bad)))
+    if not ok:
+        raise PvrlError("view_ensemble expects fp32 [N, C] predictions, int64 ids / labels / counts and an int32 flag on one device")
+    lib().call("pvrl_view_ensemble", _ptr(preds), _ld(preds), _ptr(clip_ids), _ptr(labels), N, C, int(num_clips),
+               0 if mode == "sum" else 1, _ptr(video_preds), _ld(video_preds), V, _ptr(video_labels), _ptr(clip_count), _ptr(bad),
+               _stream())
 
 
 def embed_table(pos, time, bias, N, T):

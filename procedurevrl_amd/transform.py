@@ -113,3 +113,63 @@ def decoded_train_batch(cfg, frames_u8):
         params = [spatial_sampling_params(H0, W0, -1, d.TRAIN_JITTER_SCALES[0], d.TRAIN_JITTER_SCALES[1], d.TRAIN_CROP_SIZE,
                                           d.RANDOM_FLIP, d.INV_UNIFORM_SAMPLE) for _ in range(B)]
     return DecodedClips(frames_u8, params, d.MEAN, d.STD, d.TRAIN_CROP_SIZE)
+
+
+class DecodedViews(DecodedClips):
+    """Decoded clips that SHARE source slabs: `frames` uint8 [S, T, H0, W0, 3], `params` int32 [B, 5] and `src` int32 [B] with
+    0 <= src[b] < S -- output clip b is `params[b]` applied to slab `src[b]` (the three spatial crops of a test view from one
+    decoded copy).  `shape[0]` is B, the number of output clips; `ops.frames_u8_patchify` / `ops.frames_u8_to_f32` dispatch on
+    the class to the `_views` kernels, which are bit-equal to the plain ones on `frames[src]`."""
+
+    def __init__(self, frames, params, src, mean, std, crop_size):
+        assert frames.dtype == torch.uint8 and frames.dim() == 5 and frames.shape[-1] == 3
+        self.frames = frames.contiguous()
+        p = torch.as_tensor(params, dtype=torch.int32).reshape(-1, 5)
+        s = torch.as_tensor(src, dtype=torch.int32).reshape(-1)
+        assert s.shape[0] == p.shape[0]
+        self.params_host = p.cpu()
+        self.params = p.to(frames.device)
+        self.src_host = s.cpu()
+        self.src = s.to(frames.device)
+        self.mean = [float(v) for v in mean]
+        self.std = [float(v) for v in std]
+        self.crop = int(crop_size)
+
+    @property
+    def shape(self):
+        return torch.Size((self.src_host.shape[0], 3, self.frames.shape[1], self.crop, self.crop))
+
+
+def _test_crop_index(num_crops, clip_index):
+    """lib/datasets/epickitchens.py:131-135: crop `index % 3` of three, the centre crop when there is one; anything else is
+    left undefined by the reference."""
+    if num_crops == 3:
+        return clip_index % 3
+    if num_crops == 1:
+        return 1
+    raise NotImplementedError(f"TEST.NUM_SPATIAL_CROPS = {num_crops}: the reference defines 1 and 3 (epickitchens.py:131-135)")
+
+
+def decoded_test_views(cfg, frames_u8):
+    """The test batch of decoded temporal views, uint8 [S, T, H0, W0, 3] (one slab per view) -> DecodedViews of
+    S * TEST.NUM_SPATIAL_CROPS clips in the reference's index order: clip s * K + k is crop k of slab s
+    (epickitchens.py:124-135 decodes the view once per crop; here the crops name the one uploaded slab).  The params are
+    `spatial_sampling_params(H0, W0, k, c, c, c)` with c = DATA.TEST_CROP_SIZE, called per clip as the reference calls
+    spatial_sampling: each call consumes one np.random.uniform draw even though min == max."""
+    S, T, H0, W0, _ = frames_u8.shape
+    K, c = int(cfg.TEST.NUM_SPATIAL_CROPS), int(cfg.DATA.TEST_CROP_SIZE)
+    crops = [_test_crop_index(K, k) for k in range(K)]
+    params = [spatial_sampling_params(H0, W0, k, c, c, c) for _ in range(S) for k in crops]
+    src = [s for s in range(S) for _ in crops]
+    return DecodedViews(frames_u8, params, src, cfg.DATA.MEAN, cfg.DATA.STD, c)
+
+
+def decoded_test_batch(cfg, frames_u8, clip_index):
+    """The one-slab-per-clip form of `decoded_test_views`, for a loader that already replicated the view per crop:
+    uint8 [B, T, H0, W0, 3] and the B dataset indices -> DecodedClips, crop index `clip_index % K`."""
+    B, T, H0, W0, _ = frames_u8.shape
+    K, c = int(cfg.TEST.NUM_SPATIAL_CROPS), int(cfg.DATA.TEST_CROP_SIZE)
+    idx = [int(i) for i in (clip_index.tolist() if torch.is_tensor(clip_index) else clip_index)]
+    assert len(idx) == B
+    params = [spatial_sampling_params(H0, W0, _test_crop_index(K, i), c, c, c) for i in idx]
+    return DecodedClips(frames_u8, params, cfg.DATA.MEAN, cfg.DATA.STD, c)

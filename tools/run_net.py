@@ -57,7 +57,7 @@ def main():
     args = parse_args()
     cfg = load_config(args)
     from procedurevrl_amd.train_net import train
-    from procedurevrl_amd.test_net import test
+    from procedurevrl_amd.multiview import test          # (EPIC-Kitchens: verb / noun meter; otherwise test_net.test)
     if cfg.SYNTHETIC.ENABLE:        # offline stand-ins for the embedding files the yaml names (TRAIN.LABEL_EMB, DEV.TEST_LANG_EMB)
         from procedurevrl_amd.datasets import synthetic_label_emb
         if cfg.TRAIN.ENABLE and isinstance(cfg.TRAIN.LABEL_EMB, str) and not os.path.exists(cfg.TRAIN.LABEL_EMB):
