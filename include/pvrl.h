@@ -204,6 +204,26 @@ int pvrl_attn_bwd(const void* qkv, int64_t ld, int64_t nseq, int64_t S, int64_t 
                   const void* o_cls, const void* d_o, const void* d_o_cls, int64_t ldo, const float* lse, float* dvec,
                   void* dqkv, void* dqkv_cls, int64_t ldd, void* stream);
 
+/* Long-sequence attention, head_dim 64, no masks, any `scale`, 1 <= S <= PVRL_ATTN_LONG_MAX_S (PVRL_EINVAL beyond, nothing launched):
+ * the joint space-time scheme of the reference (Block.forward, vit.py:124-127: ONE sequence of 1 + N*T tokens per clip) and every
+ * sequence longer than the 416 tokens pvrl_attn_fwd keeps in LDS (csrc/attn_long.hip).  K / V are streamed through LDS in tiles of
+ * PVRL_ATTN_LONG_KT keys with an online softmax (running max and sum in fp32, P rounded to the operand type only as the second
+ * product's operand); a workgroup owns PVRL_ATTN_LONG_QT queries of one (sequence, head).  Operands, addressing modes and the *_cls
+ * side buffers are those of pvrl_attn_fwd / _bwd (mode 1 with any T).  lse: [nseq][H][S] fp32.
+ * Backward: P is recomputed from lse; a query-block kernel sweeps the keys for dQ (and writes D = rowsum(dO * O) into `workspace`), a
+ * key-block kernel sweeps the queries for dK / dV: no atomics, no hand-off between workgroups, bit-equal from run to run.
+ * workspace >= pvrl_attn_long_bwd_workspace_bytes(nseq, S, H) (the caller keeps it to itself for the length of the call). */
+#define PVRL_ATTN_LONG_KT 64
+#define PVRL_ATTN_LONG_QT 128
+#define PVRL_ATTN_LONG_MAX_S 8192
+int pvrl_attn_long_fwd(const void* qkv, int64_t ld, int64_t nseq, int64_t S, int64_t H, int mode, int64_t T,
+                       int64_t cls_base, float scale, void* o, void* o_cls, int64_t ldo, float* lse, void* stream);
+int64_t pvrl_attn_long_bwd_workspace_bytes(int64_t nseq, int64_t S, int64_t H);
+int pvrl_attn_long_bwd(const void* qkv, int64_t ld, int64_t nseq, int64_t S, int64_t H, int mode, int64_t T,
+                       int64_t cls_base, float scale, const void* o, const void* o_cls, const void* d_o,
+                       const void* d_o_cls, int64_t ldo, const float* lse, void* dqkv, void* dqkv_cls, int64_t ldd,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+
 /* The same attention (mode 1 addressing) for the cls query of every sequence ONLY -- the spatial attention of the encoder's LAST block,
  * of whose output only x[:, 0] is read (vit.py:418-421; csrc/attn_cls.hip).  Forward: o_cls [nseq][H*64] and lse[(seq*H + h)*S + 0] (the
  * other lse entries are not written).  Backward: dO is taken to be zero for every patch query: dK / dV of all S tokens and zeros for the

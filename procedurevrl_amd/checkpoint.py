@@ -156,15 +156,17 @@ def load_pretrained(model, cfg):
         cls_pe = pe[0, 0, :].unsqueeze(0).unsqueeze(1)
         other = F.interpolate(pe[0, 1:, :].unsqueeze(0).transpose(1, 2), size=(n_tok - 1), mode="nearest").transpose(1, 2)
         state["pos_embed"] = torch.cat((cls_pe, other), 1)
-    nf = model.time_embed.shape[1]
-    if "time_embed" in state and state["time_embed"].size(1) != nf:
-        state["time_embed"] = F.interpolate(state["time_embed"].transpose(1, 2), size=(nf), mode="nearest").transpose(1, 2)
+    if hasattr(model, "time_embed"):        # (`space_only` has none, vit.py:215: a checkpoint's time_embed is then an unexpected key)
+        nf = model.time_embed.shape[1]
+        if "time_embed" in state and state["time_embed"].size(1) != nf:
+            state["time_embed"] = F.interpolate(state["time_embed"].transpose(1, 2), size=(nf), mode="nearest").transpose(1, 2)
     new_state = OrderedDict(state)
-    for key in state:                       # helpers.py:223-238
-        if "blocks" in key and "attn" in key and "temporal_attn" not in key:
-            new_state.setdefault(key.replace("attn", "temporal_attn"), state[key])
-        if "blocks" in key and "norm1" in key and "temporal_norm1" not in key:
-            new_state.setdefault(key.replace("norm1", "temporal_norm1"), state[key])
+    if getattr(model, "attention_type", "divided_space_time") == "divided_space_time":      # helpers.py:223-238
+        for key in state:
+            if "blocks" in key and "attn" in key and "temporal_attn" not in key:
+                new_state.setdefault(key.replace("attn", "temporal_attn"), state[key])
+            if "blocks" in key and "norm1" in key and "temporal_norm1" not in key:
+                new_state.setdefault(key.replace("norm1", "temporal_norm1"), state[key])
     missing, unexpected = model.load_state_dict(new_state, strict=False)
     print("\nMissing keys: ", missing, "\nUnexpected_keys: ", unexpected)
 

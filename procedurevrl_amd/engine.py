@@ -13,6 +13,10 @@ addressed in place by the attention kernel, and the cls rows are a small suffix,
 three residual branches of a block are 3 LayerNorms + 7 GEMMs + 2 attention launches and no
 copy kernels.  Activations are GEMM operands in the library's 16-bit type (fp16 by default); the cls rows of the residual stream,
 LayerNorm statistics, softmax statistics and all parameter gradients are fp32.
+
+TIMESFORMER.ATTENTION_TYPE 'joint_space_time' / 'space_only' (vit.py:124-127) take ONE undivided block path on the same row layout
+(`_block_fwd_undivided` / `_block_bwd_undivided`): a sample's sequence is its cls row plus its N*T patch rows (the attention kernels'
+mode 1 with T = 1); `space_only` runs it on B*T one-frame pseudo-clips and averages a clip's cls rows in front of the final norm.
 """
 import math
 import os
@@ -441,6 +445,10 @@ class EncoderEngine(GraphReplay):
     def __init__(self, model):
         """`model` is a procedurevrl_amd.vit.VisionTransformer (same parameter names as the reference)."""
         self.m = model
+        # 'space_only' / 'joint_space_time' (vit.py:124-127): ONE attention over each sample's tokens and an MLP per block -- the undivided
+        # block path below (_block_fwd_undivided / _block_bwd_undivided); `space_only` runs it on B * T one-frame pseudo-clips
+        self.undivided = getattr(model, "attention_type", "divided_space_time") != "divided_space_time"
+        self.space_only = getattr(model, "attention_type", "") == "space_only"
         self.C = model.embed_dim
         self.H = model.num_heads
         self.scale = (self.C // self.H) ** -0.5
@@ -500,8 +508,9 @@ class EncoderEngine(GraphReplay):
         m = self.m
         plist = [(m.patch_embed.proj.weight, False)]
         for blk in m.blocks:
-            plist += [(blk.temporal_attn.qkv.weight, True), (blk.temporal_attn.proj.weight, True),
-                      (blk.temporal_fc.weight, True), (blk.attn.qkv.weight, True), (blk.attn.proj.weight, True),
+            if not self.undivided:
+                plist += [(blk.temporal_attn.qkv.weight, True), (blk.temporal_attn.proj.weight, True), (blk.temporal_fc.weight, True)]
+            plist += [(blk.attn.qkv.weight, True), (blk.attn.proj.weight, True),
                       (blk.mlp.fc1.weight, True), (blk.mlp.fc2.weight, True)]
         self.weights.refresh(plist, force=self._capturing == "fwd")
 
@@ -539,6 +548,8 @@ class EncoderEngine(GraphReplay):
         """W_e = W_fc W_proj (and b_e) of every block whose weights changed, at the start of a forward: ONE batched launch of the twelve
         768^3 GEMMs and one of the twelve casts instead of a 16.6-us GEMM + a cast in front of every block's temporal GEMM."""
         self._fused_fresh = set()
+        if self.undivided:
+            return
         stale = [blk for blk in self.m.blocks if self._fused_temporal_stale(blk)]
         if len(stale) < 2:
             return
@@ -650,6 +661,29 @@ class EncoderEngine(GraphReplay):
                                                   s2_mean=s2_mean[i])
                 for i in range(nb)]
 
+    def _droppath_undivided(self, B, N, T, device, training):
+        """DropPath of the undivided schemes: one draw per dim-0 sample and branch (vit.py:125-126 through vit_utils.py:140-155) -- per
+        clip for `joint_space_time`, per (clip, frame) for `space_only`, whose pseudo-clips are the B here"""
+        rates = [float(r) for r in self.m.drop_path_rates]
+        nb = len(rates)
+        if not training or all(r == 0.0 for r in rates):
+            return [None] * nb
+        if self._keep is None or self._keep[0] != (tuple(rates), device):
+            self._keep = ((tuple(rates), device), torch.tensor([1.0 - r for r in rates], device=device, dtype=F32).view(nb, 1))
+        keep = self._keep[1]
+        sc = torch.floor(keep + torch.rand((nb, 2 * B), device=device)) / keep
+        s2, s3 = sc[:, :B], sc[:, B:]
+        s2_all = torch.cat([s2.repeat_interleave(N * T, dim=1), s2], 1)               # [nb, B*N*T + B]
+        s3_all = torch.cat([s3.repeat_interleave(N * T, dim=1), s3], 1)
+        return [None if rates[i] == 0.0 else dict(s2_all=s2_all[i], s3_all=s3_all[i]) for i in range(nb)]
+
+    @staticmethod
+    def expand_droppath_undivided(s_attn, s_mlp, B, N, T):
+        """pinned draws of one undivided block: s_attn / s_mlp fp32 [B] = floor(keep + u) / keep of its two DropPath calls (B: clips
+        for `joint_space_time`, (clip, frame) pairs for `space_only` with T = 1) -> the dict forward(..., droppath=[...]) takes"""
+        exp = lambda v: torch.cat([v.repeat_interleave(N * T), v]).contiguous()
+        return dict(s2_all=exp(s_attn), s3_all=exp(s_mlp))
+
     @staticmethod
     def expand_droppath(s1, s2, s3, B, N, T):
         s1_tok = s1.repeat_interleave(T).contiguous()
@@ -668,6 +702,8 @@ class EncoderEngine(GraphReplay):
             other = pos[1:].t().reshape(1, self.C, P, P)
             other = torch.nn.functional.interpolate(other, size=(Hn, Wp), mode="nearest").flatten(2)[0].t()
             pos = torch.cat([pos[:1], other], 0)
+        if self.space_only:         # no time embedding (vit.py:393): a zero row for the embedding table
+            return pos.contiguous(), torch.zeros((1, self.C), device=pos.device, dtype=pos.dtype)
         tim = m.time_embed[0]
         if tim.shape[0] != T:
             tim = torch.nn.functional.interpolate(tim.t().unsqueeze(0), size=T, mode="nearest")[0].t()
@@ -689,6 +725,14 @@ class EncoderEngine(GraphReplay):
         self._refresh_weights()
         self._refreshed = True
         self._build_fused_all()
+        frames_per_clip = 0
+        if self.space_only:
+            # every frame is a sample of its own (vit.py:174-180: PatchEmbed folds T into the batch, and nothing unfolds it before the
+            # mean over the frames' cls rows, vit.py:414-416): B * T pseudo-clips of one frame, rows (b * T + t, n)
+            if isinstance(frames, DecodedClips):
+                frames = ops.frames_u8_to_f32(frames)
+            frames_per_clip = frames.shape[2]
+            frames = frames.permute(0, 2, 1, 3, 4).reshape(-1, frames.shape[1], 1, frames.shape[3], frames.shape[4])
         B, _, T, HI, WI = frames.shape
         Wp = WI // 16
         N = (HI // 16) * Wp
@@ -712,10 +756,16 @@ class EncoderEngine(GraphReplay):
         sv["a_pe"] = a_pe if save else None
 
         if droppath is None:
-            droppath = self._droppath_all(B, N, T, dev, training)
+            droppath = (self._droppath_undivided if self.undivided else self._droppath_all)(B, N, T, dev, training)
         for i, blk in enumerate(m.blocks):
-            x = self._block_fwd(blk, x, sv, droppath[i], save, last=i == len(m.blocks) - 1)
+            if self.undivided:
+                x = self._block_fwd_undivided(blk, x, sv, droppath[i], save)
+            else:
+                x = self._block_fwd(blk, x, sv, droppath[i], save, last=i == len(m.blocks) - 1)
 
+        if frames_per_clip:         # vit.py:414-416: the mean over the frames, in front of the final norm (only x[:, 0] is read)
+            sv["frames_per_clip"] = frames_per_clip
+            x = _X(x.p, x.c.view(-1, frames_per_clip, C).mean(1))
         feat, mean, rstd = ops.layernorm_fwd(x.c, m.norm.weight.detach(), m.norm.bias.detach(), self.eps,
                                              out_dtype=F32)
         self._refreshed = False
@@ -856,6 +906,111 @@ class EncoderEngine(GraphReplay):
                                      lse_s=lse_s, h_m=h_m, st_m=(mean_m, rstd_m), u=u, g=g, dp=dp, pruned=prune, cls_attn=cls_attn))
         return x3
 
+    # ------------------------------------------------------------------ undivided schemes (space_only / joint_space_time)
+    def _attn_undivided(self, qkv, B, S, R, o):
+        """one sequence per sample: its cls row R + b, then its S - 1 patch rows -- the kernels' mode 1 with T = 1, whose token-0 side
+        buffers are then the cls rows of the same matrices.  Up to ops.ATTN_MAX_S tokens the whole-sequence kernels, beyond them the
+        streamed ones (ops.attn_uses_long)."""
+        fwd = ops.attn_long_fwd if ops.attn_uses_long(S) else ops.attn_fwd
+        return fwd(qkv, B, S, self.H, self.scale, mode=1, T=1, cls_base=R, o=o[:R], o_cls=o[R:])[2]
+
+    def _block_fwd_undivided(self, blk, x0, sv, dp, save):
+        """x += dp * proj(attn(norm1(x))); x += dp * mlp(norm2(x))   (Block.forward, vit.py:124-127) on the rows of `_X`.  No pruning of
+        the last block; the cls rows' projection and MLP run in fp32 (cls_fp32) as in the divided path."""
+        L = lib()
+        B, T, N, R, M = sv["B"], sv["T"], sv["N"], sv["R"], sv["M"]
+        C = self.C
+        dev = x0.c.device
+        split, epi_res = sv["split"], self._epi_resid()
+        s2_all = dp["s2_all"] if dp else None
+        s3_all = dp["s3_all"] if dp else None
+        row = lambda s, a, b: s[a:b] if s is not None else None
+        P = lambda t: t.detach()
+
+        # ---- attention over all 1 + N * T tokens of a sample ----
+        h_s, mean_s, rstd_s = ops.layernorm_fwd(x0.all(), P(blk.norm1.weight), P(blk.norm1.bias), self.eps)
+        qkv_s = ops.gemm_nt(h_s, self._weight(blk.attn.qkv.weight).w, L.PVRL_EPI_BF16, bias=P(blk.attn.qkv.bias))
+        o_s = torch.empty((M, C), device=dev, dtype=OP16)
+        lse_s = self._attn_undivided(qkv_s, B, N * T + 1, R, o_s)
+        x1 = _X.new(R, B, C, dev, split)
+        wproj = self._weight(blk.attn.proj.weight).w
+        ops.gemm_nt(o_s[:R], wproj, epi_res, bias=P(blk.attn.proj.bias), rowscale=row(s2_all, 0, R), aux=x0.p, out0=x1.p)
+        if self.cls_fp32:
+            ops.cls_linear(o_s[R:].float(), P(blk.attn.proj.weight), P(blk.attn.proj.bias), rowscale=row(s2_all, R, M),
+                           biasscale=row(s2_all, R, M), aux=x0.c, out=x1.c)
+        else:
+            ops.gemm_nt(o_s[R:], wproj, L.PVRL_EPI_RESID_F32, bias=P(blk.attn.proj.bias), rowscale=row(s2_all, R, M), aux=x0.c, out0=x1.c)
+
+        # ---- MLP ----
+        x2 = _X.new(R, B, C, dev, split)
+        h_m, mean_m, rstd_m = ops.layernorm_fwd(x1.all(), P(blk.norm2.weight), P(blk.norm2.bias), self.eps)
+        u, g = ops.gemm_nt(h_m, self._weight(blk.mlp.fc1.weight).w, L.PVRL_EPI_GELU, bias=P(blk.mlp.fc1.bias))
+        w2 = self._weight(blk.mlp.fc2.weight).w
+        ops.gemm_nt(g[:R], w2, epi_res, bias=P(blk.mlp.fc2.bias), rowscale=row(s3_all, 0, R), aux=x1.p, out0=x2.p)
+        if self.cls_fp32:       # (the 16-bit cls rows of h_m / u / g stay what the backward reads)
+            hc, _, _ = ops.layernorm_fwd(x1.c, P(blk.norm2.weight), P(blk.norm2.bias), self.eps, out_dtype=F32, save_stats=False)
+            gc = ops.cls_linear(hc, P(blk.mlp.fc1.weight), P(blk.mlp.fc1.bias), gelu=True)
+            ops.cls_linear(gc, P(blk.mlp.fc2.weight), P(blk.mlp.fc2.bias), rowscale=row(s3_all, R, M), biasscale=row(s3_all, R, M),
+                           aux=x1.c, out=x2.c)
+        else:
+            ops.gemm_nt(g[R:], w2, L.PVRL_EPI_RESID_F32, bias=P(blk.mlp.fc2.bias), rowscale=row(s3_all, R, M), aux=x1.c, out0=x2.c)
+        if save:
+            sv["blocks"].append(dict(undivided=True, x0=x0, x1=x1, h_s=h_s, st_s=(mean_s, rstd_s), qkv_s=qkv_s, o_s=o_s, lse_s=lse_s,
+                                     h_m=h_m, st_m=(mean_m, rstd_m), u=u, g=g, dp=dp))
+        return x2
+
+    def _block_bwd_undivided(self, blk, s, sv, dx, gs, dy, has_prev, prev_dp):
+        """backward of _block_fwd_undivided; dy = 16-bit(s3 * dx) [M, C] arrives from the caller, the return value is the same for the
+        block in front (or, for block 0, the unscaled 16-bit copy of dx's patch rows for the patch-embedding weight gradient)"""
+        L = lib()
+        B, T, N, R, M = sv["B"], sv["T"], sv["N"], sv["R"], sv["M"]
+        C, H = self.C, self.H
+        dev = dx.c.device
+        dp = s["dp"]
+        s2_all = dp["s2_all"] if dp else None
+        row = lambda v, a, b: v[a:b] if v is not None else None
+        P = lambda t: t.detach()
+        defer = self._ln_defer
+
+        def wgrad(d, xin, lin):
+            (dw, bw), (dbias, _) = gs.target(lin.weight, fused=True), gs.target(lin.bias, fused=True)
+            self._wgrad(d, xin, dw, dbias, bw, gscale=gs.inv, nonfinite=gs.bad)
+
+        def lnbwd(dh, x, st, ln, dxs, dxs_scale):
+            (dg, bg), (db, _) = gs.target(ln.weight, fused=True), gs.target(ln.bias, fused=True)
+            ops.layernorm_bwd(dh, x, st[0], st[1], P(ln.weight), dg, db, dx_in=dx.all(), dx_out=dx.all(), beta_acc=bg,
+                              dxs=dxs, dxs_scale=dxs_scale, gscale=gs.inv, nonfinite=gs.bad, defer=defer)
+
+        # ---- MLP ----
+        wgrad(dy, s["g"], blk.mlp.fc2)
+        du = ops.gemm_nt(dy, self._weight(blk.mlp.fc2.weight).t, L.PVRL_EPI_DGELU, aux=s["u"])
+        wgrad(du, s["h_m"], blk.mlp.fc1)
+        dh = ops.gemm_nt(du, self._weight(blk.mlp.fc1.weight).t, L.PVRL_EPI_BF16)
+        del du
+        dps = torch.empty((M, C), device=dev, dtype=OP16)
+        lnbwd(dh, s["x1"].all(), s["st_m"], blk.norm2, dps[:R], row(s2_all, 0, R))       # also emits 16-bit(s2 * dx[:R])
+        ops.cast_scale(dx.c, row(s2_all, R, M), out=dps[R:])
+
+        # ---- attention ----
+        wgrad(dps, s["o_s"], blk.attn.proj)
+        do = ops.gemm_nt(dps, self._weight(blk.attn.proj.weight).t, L.PVRL_EPI_BF16)
+        del dps
+        S = N * T + 1
+        dqkv = torch.empty((M, 3 * C), device=dev, dtype=OP16)
+        bwd = ops.attn_long_bwd if ops.attn_uses_long(S) else ops.attn_bwd
+        bwd(s["qkv_s"], s["o_s"][:R], s["o_s"][R:], do[:R], do[R:], s["lse_s"], B, S, H, self.scale, mode=1, T=1, cls_base=R,
+            dqkv=dqkv, dqkv_cls=dqkv[R:])
+        wgrad(dqkv, s["h_s"], blk.attn.qkv)
+        dh = ops.gemm_nt(dqkv, self._weight(blk.attn.qkv.weight).t, L.PVRL_EPI_BF16)
+        del dqkv, do
+        s3p = prev_dp["s3_all"] if (has_prev and prev_dp) else None
+        dy_next = torch.empty((M if has_prev else R, C), device=dev, dtype=OP16)
+        lnbwd(dh, s["x0"].all(), s["st_s"], blk.norm1, dy_next[:R], row(s3p, 0, R))
+        if has_prev:
+            ops.cast_scale(dx.c, row(s3p, R, M), out=dy_next[R:])
+        self.flush_wgrads()
+        return dy_next
+
     # ------------------------------------------------------------------ HIP graphs (GraphReplay)
     def _eager_forward(self, frames, training, save):
         return self._forward(frames, training, None, save)
@@ -878,7 +1033,8 @@ class EncoderEngine(GraphReplay):
     def _enc_params(self):
         """the parameters whose gradients backward() writes"""
         m = self.m
-        ps = [m.cls_token, m.pos_embed, m.time_embed] + list(m.patch_embed.parameters()) + list(m.norm.parameters())
+        ps = [m.cls_token, m.pos_embed] + ([] if self.space_only else [m.time_embed])
+        ps += list(m.patch_embed.parameters()) + list(m.norm.parameters())
         for blk in m.blocks:
             ps += list(blk.parameters())
         return [p for p in ps if p.requires_grad]
@@ -929,8 +1085,12 @@ class EncoderEngine(GraphReplay):
             self._undef(dx.p)
         mean, rstd = sv["norm_stats"]
         (dg, bg), (db, bb) = gs.target(m.norm.weight, fused=True), gs.target(m.norm.bias, fused=True)
+        fpc = sv.get("frames_per_clip", 0)
+        dxm = torch.empty_like(sv["x_final"].c) if fpc else dx.c
         ops.layernorm_bwd(dfeat.contiguous(), sv["x_final"].c, mean, rstd, m.norm.weight.detach(), dg, db,
-                          dx_out=dx.c, beta_acc=bg, gscale=gs.inv, nonfinite=gs.bad)
+                          dx_out=dxm, beta_acc=bg, gscale=gs.inv, nonfinite=gs.bad)
+        if fpc:                     # `space_only`: the final norm saw the mean of a clip's frames (vit.py:414-416)
+            dx.c.view(-1, fpc, self.C).copy_((dxm / fpc).unsqueeze(1).expand(-1, fpc, -1))
         # dy = bf16(DropPath-scale * dx) is the operand of each block's first backward GEMMs; after the first block it is
         # emitted by the previous block's last LayerNorm-backward kernel instead of a separate cast pass.
         s3 = sv["blocks"][last]["dp"]["s3_all"] if sv["blocks"][last]["dp"] else None
@@ -968,12 +1128,13 @@ class EncoderEngine(GraphReplay):
         self._acc(gs, m.cls_token, dcls_rows.view(1, 1, C))
         dpos = torch.cat([dcls_rows.unsqueeze(0), G.sum(1)], 0)
         dtime = G.sum(0)
-        pos_p, tim_p = m.pos_embed, m.time_embed
-        if pos_p.shape[1] != N + 1 or tim_p.shape[1] != T:
+        pos_p, tim_p = m.pos_embed, None if self.space_only else m.time_embed
+        if pos_p.shape[1] != N + 1 or (tim_p is not None and tim_p.shape[1] != T):
             raise NotImplementedError("training with resized pos/time embeddings is not supported (reference "
                                       "resizes at inference only, vit.py:374)")
         self._acc(gs, pos_p, dpos.unsqueeze(0))
-        self._acc(gs, tim_p, dtime.unsqueeze(0))
+        if tim_p is not None:
+            self._acc(gs, tim_p, dtime.unsqueeze(0))
         self.flush_wgrads()
         self._finish_deferred(gs)
         if gs.scale is not None:
@@ -993,6 +1154,8 @@ class EncoderEngine(GraphReplay):
         B, T, N, R, M = sv["B"], sv["T"], sv["N"], sv["R"], sv["M"]
         C, H = self.C, self.H
         dev = dx.c.device
+        if s.get("undivided"):
+            return self._block_bwd_undivided(blk, s, sv, dx, gs, dy, has_prev, prev_dp)
         dp = s["dp"]
         s1_tok = dp["s1_tok"] if dp else None
         s2_seq = dp["s2_seq"] if dp else None

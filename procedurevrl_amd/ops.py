@@ -8,7 +8,7 @@ import ctypes
 
 import torch
 
-from ._lib import lib, PvrlError, operand_torch_dtype
+from ._lib import lib, PvrlError, header_constants, operand_torch_dtype
 
 OP16 = operand_torch_dtype()     # the library flavour's 16-bit operand type: torch.bfloat16 (default) or torch.float16
 F32 = torch.float32
@@ -504,6 +504,55 @@ def attn_bwd(qkv, o, o_cls, d_o, d_o_cls, lse, nseq, S, H, scale, mode=0, T=1, c
     L.call("pvrl_attn_bwd", _ptr(qkv), _ld(qkv), nseq, S, H, mode, T, cls_base, float(scale), 1 if causal else 0,
            _ptr(kpm), _ptr(o), _ptr(o_cls), _ptr(d_o), _ptr(d_o_cls), _ld(o), _ptr(lse), _ptr(dvec), _ptr(dqkv),
            _ptr(dqkv_cls), _ld(dqkv), _stream())
+    return dqkv, dqkv_cls
+
+
+# the long-sequence kernels' tiles and limits (include/pvrl.h; read from the header, so importing them needs no built library)
+_HC = header_constants()
+ATTN_LONG_KT, ATTN_LONG_QT, ATTN_LONG_MAX_S = _HC["PVRL_ATTN_LONG_KT"], _HC["PVRL_ATTN_LONG_QT"], _HC["PVRL_ATTN_LONG_MAX_S"]
+ATTN_MAX_S = 416      # the longest sequence pvrl_attn_fwd / _bwd keep in LDS (csrc/attn_common.h, ATT_ROWS_LONG)
+
+
+def attn_uses_long(S):
+    """the undivided schemes' attention dispatch: sequences of more than ATTN_MAX_S tokens take attn_long_fwd / _bwd"""
+    return S > ATTN_MAX_S
+
+
+def attn_long_fwd(qkv, nseq, S, H, scale, mode=0, T=1, cls_base=0, o=None, o_cls=None, lse=None):
+    """attn_fwd for 1 <= S <= ATTN_LONG_MAX_S without masks (pvrl_attn_long_fwd: streamed K / V, online softmax)"""
+    L = lib()
+    _chk2d(qkv, OP16)
+    if o is None:
+        o = torch.empty((nseq * S if mode == 0 else cls_base, H * 64), device=qkv.device, dtype=OP16)
+    if mode == 1 and o_cls is None:
+        o_cls = torch.empty((nseq, H * 64), device=qkv.device, dtype=OP16)
+    if lse is None:
+        lse = torch.empty((nseq, H, S), device=qkv.device, dtype=F32)
+    if o_cls is not None:
+        assert _ld(o_cls) == _ld(o)
+    L.call("pvrl_attn_long_fwd", _ptr(qkv), _ld(qkv), nseq, S, H, mode, T, cls_base, float(scale), _ptr(o), _ptr(o_cls), _ld(o),
+           _ptr(lse), _stream())
+    return o, o_cls, lse
+
+
+def attn_long_bwd(qkv, o, o_cls, d_o, d_o_cls, lse, nseq, S, H, scale, mode=0, T=1, cls_base=0, dqkv=None, dqkv_cls=None):
+    """backward of attn_long_fwd (pvrl_attn_long_bwd); deterministic, D = rowsum(dO * O) in the shared workspace"""
+    L = lib()
+    _chk2d(qkv, OP16)
+    if dqkv is None:
+        dqkv = torch.empty_like(qkv)
+    if mode == 1 and dqkv_cls is None:
+        dqkv_cls = torch.empty((nseq, qkv.shape[1]), device=qkv.device, dtype=OP16)
+    if dqkv_cls is not None:
+        assert _ld(dqkv_cls) == _ld(dqkv)
+    if o_cls is not None:
+        assert _ld(o_cls) == _ld(o) == _ld(d_o) == _ld(d_o_cls)
+    else:
+        assert _ld(o) == _ld(d_o)
+    nbytes = L.call("pvrl_attn_long_bwd_workspace_bytes", nseq, S, H)
+    ws = workspace(nbytes, qkv.device, "attn_long")
+    L.call("pvrl_attn_long_bwd", _ptr(qkv), _ld(qkv), nseq, S, H, mode, T, cls_base, float(scale), _ptr(o), _ptr(o_cls),
+           _ptr(d_o), _ptr(d_o_cls), _ld(o), _ptr(lse), _ptr(dqkv), _ptr(dqkv_cls), _ld(dqkv), _ptr(ws), ws.numel(), _stream())
     return dqkv, dqkv_cls
 
 

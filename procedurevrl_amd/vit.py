@@ -48,20 +48,21 @@ class Attention(nn.Module):
         self.proj = nn.Linear(dim, dim)
 
 
+ATTENTION_TYPES = ("divided_space_time", "space_only", "joint_space_time")
+
+
 class Block(nn.Module):
     def __init__(self, dim, num_heads, mlp_ratio=4.0, qkv_bias=False, qk_scale=None, drop_path=0.1,
                  norm_layer=nn.LayerNorm, attention_type="divided_space_time"):
         super().__init__()
-        if attention_type != "divided_space_time":
-            raise NotImplementedError(
-                f"TIMESFORMER.ATTENTION_TYPE={attention_type!r}: only 'divided_space_time' (every shipped config, "
-                "vit.py:124-127) is built on the HIP path")
+        assert attention_type in ATTENTION_TYPES, attention_type       # vit.py:100
         self.attention_type = attention_type
         self.norm1 = norm_layer(dim)
         self.attn = Attention(dim, num_heads=num_heads, qkv_bias=qkv_bias, qk_scale=qk_scale)
-        self.temporal_norm1 = norm_layer(dim)
-        self.temporal_attn = Attention(dim, num_heads=num_heads, qkv_bias=qkv_bias, qk_scale=qk_scale)
-        self.temporal_fc = nn.Linear(dim, dim)
+        if attention_type == "divided_space_time":      # vit.py:107-111: the undivided schemes have no temporal branch
+            self.temporal_norm1 = norm_layer(dim)
+            self.temporal_attn = Attention(dim, num_heads=num_heads, qkv_bias=qkv_bias, qk_scale=qk_scale)
+            self.temporal_fc = nn.Linear(dim, dim)
         self.drop_path_rate = drop_path
         self.norm2 = norm_layer(dim)
         self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio))
@@ -99,11 +100,12 @@ class VisionTransformer(nn.Module):
         num_patches = self.patch_embed.num_patches
         self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
         self.pos_embed = nn.Parameter(torch.zeros(1, num_patches + 1, embed_dim))
-        self.time_embed = nn.Parameter(torch.zeros(1, num_frames, embed_dim))
         # vit.py:209,214: identity at p = 0 (asserted above); kept as attributes because the linear-probing loop reaches for them
         # (`model.model.pos_drop.eval()`, tools/train_net.py:72-85)
         self.pos_drop = nn.Dropout(p=drop_rate)
-        self.time_drop = nn.Dropout(p=drop_rate)
+        if attention_type != "space_only":              # vit.py:215-217
+            self.time_embed = nn.Parameter(torch.zeros(1, num_frames, embed_dim))
+            self.time_drop = nn.Dropout(p=drop_rate)
         dpr = [x.item() for x in torch.linspace(0, drop_path_rate, depth)]   # vit.py:220
         self.drop_path_rates = dpr
         self.blocks = nn.ModuleList([

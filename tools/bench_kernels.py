@@ -188,6 +188,44 @@ def main():
         us = timeit(lambda: ops.rand_augment_u8(fr, plan))
         rows.append(("randaug u8 4x32x256x456, 2 layers [GB/s]", us, 4.0 * fr.numel() / us / 1e3))
 
+    if want("attn_long"):
+        # The streamed long-sequence attention (csrc/attn_long.hip) at joint space-time attention's shapes -- 32 clips x 12 heads x 1,569
+        # tokens (8 x 224^2) and 4 x 12 x 6,273 (32 x 224^2) -- in alternating rounds with torch's scaled_dot_product_attention on the
+        # same values in the same process; the median round counts.  FLOPs: 4 S^2 64 per (clip, head) forward; the backward's EXECUTED
+        # products: seven here (S and dP are formed in both backward kernels), five assumed for the baseline.
+        import statistics
+        import torch.nn.functional as F
+        OP = ops.OP16
+        for Bl, Hl, Sl in ((32, 12, 1569), (4, 12, 6273)):
+            Rl = Bl * (Sl - 1)
+            qkv = rnd(Rl + Bl, 3 * Hl * 64).to(OP)
+            do = rnd(Rl + Bl, Hl * 64).to(OP)
+            o = torch.empty(Rl + Bl, Hl * 64, device=DEV, dtype=OP)
+            dq = torch.empty(Rl + Bl, 3 * Hl * 64, device=DEV, dtype=OP)
+            kw = dict(mode=1, T=1, cls_base=Rl)
+            ff = lambda: ops.attn_long_fwd(qkv, Bl, Sl, Hl, 0.125, o=o[:Rl], o_cls=o[Rl:], **kw)
+            lse = ff()[2]
+            fb = lambda: ops.attn_long_bwd(qkv, o[:Rl], o[Rl:], do[:Rl], do[Rl:], lse, Bl, Sl, Hl, 0.125, dqkv=dq, dqkv_cls=dq[Rl:], **kw)
+            # the same sequences as [B, H, S, 64] tensors: cls row first, then the clip's patch rows
+            seq = torch.cat([qkv[Rl:].view(Bl, 1, -1), qkv[:Rl].view(Bl, Sl - 1, -1)], 1).view(Bl, Sl, 3, Hl, 64).permute(2, 0, 3, 1, 4)
+            q, k, v = (t.contiguous().requires_grad_(True) for t in seq)
+            dos = torch.cat([do[Rl:].view(Bl, 1, -1), do[:Rl].view(Bl, Sl - 1, -1)], 1).view(Bl, Sl, Hl, 64).permute(0, 2, 1, 3).contiguous()
+            sf = lambda: F.scaled_dot_product_attention(q, k, v, scale=0.125)
+            os_ = sf()
+            sb = lambda: torch.autograd.grad(os_, (q, k, v), dos, retain_graph=True)
+            t = {n: [] for n in ("ff", "sf", "fb", "sb")}
+            for _ in range(5):
+                for n, fn in (("ff", ff), ("sf", sf), ("fb", fb), ("sb", sb)):
+                    t[n].append(timeit(fn, reps=5, warm=1))
+            med = {n: statistics.median(v) for n, v in t.items()}
+            fl = 4.0 * Bl * Hl * Sl * Sl * 64
+            tag = f"{Bl}x{Hl}xS{Sl}"
+            rows.append((f"attn_long fwd {tag}", med["ff"], fl / med["ff"] / 1e6))
+            rows.append((f"torch sdpa fwd {tag}", med["sf"], fl / med["sf"] / 1e6))
+            rows.append((f"attn_long bwd {tag} (7 products)", med["fb"], 3.5 * fl / med["fb"] / 1e6))
+            rows.append((f"torch sdpa bwd {tag} (5 products)", med["sb"], 2.5 * fl / med["sb"] / 1e6))
+            del q, k, v, os_, dos, seq
+
     for name, us, rate in rows:
         print(f"{name:42s} {us:9.1f} us   {rate:9.1f} {'TFLOP/s' if 'GB/s' not in name else 'GB/s'}")
 
