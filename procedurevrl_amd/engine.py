@@ -25,6 +25,7 @@ import torch
 
 from . import ops
 from ._lib import lib
+from .graphs import GraphReplay, drop_graphs_quietly      # (their home; imported from here by mvit.py and callers)
 from .transform import DecodedClips
 
 OP16 = ops.OP16
@@ -209,236 +210,6 @@ class _X:
 
     def patch(self):
         return self.p if self.full is not None else ops.SplitRows(self.p, None)
-
-
-def drop_graphs_quietly(graphs):
-    """clear a dict / list that holds captured HIP graphs, with the device idle (see GraphReplay.release_graphs)"""
-    if not graphs:
-        return
-    try:
-        if torch.cuda.is_available():
-            torch.cuda.synchronize()
-    except Exception:
-        pass
-    graphs.clear()
-    try:        # ... and their memory pool goes back NOW, still with the device idle, not whenever the allocator next trims its cache
-        if torch.cuda.is_available():
-            torch.cuda.synchronize()
-            torch.cuda.empty_cache()
-    except Exception:
-        pass
-
-
-class GraphReplay:
-    """HIP-graph replay of an encoder engine's training / inference step.
-
-    One training step of the encoder is ~1,400 kernel launches (~7 ms of Python on an idle host, several times that
-    when the node's cores are contended -- measured up to 95 ms, more than the 57 ms the GPU needs).  The launch
-    sequence of a given (shape, mode) never changes, so it is captured once (torch.cuda.CUDAGraph = hipGraph; the
-    C ABI launches on the capturing stream like on any other) and replayed: forward and backward are one graph each
-    (backward: one per block when a data-parallel gradient hook is installed and the engine has staged backward),
-    sharing a memory pool so the activations saved by the forward graph are the backward graph's inputs.  What a
-    replay cannot express falls back to the eager path: pinned DropPath draws, DecodedClips inputs, gradient
-    accumulation into existing .grad tensors.
-
-    The engine provides: _eager_forward(frames, training, save), _eager_backward(dfeat), _graph_key(frames, training,
-    save), _enc_params() (the parameters whose gradients backward writes), `saved`, `grad_hook`, and consults
-    `self._capturing` ("fwd": refresh every weight copy inside the graph, "bwd": reuse them).  Optional: _bwd_begin /
-    _bwd_block / _bwd_end for staged capture.
-    """
-    GRAPH_WARMUP = 2      # eager calls of a key before it is captured (lazy workspaces / caches settle)
-    GRAPH_MAX_KEYS = 4    # captured (shape, mode) combinations kept; others run eagerly
-    _capturing = None     # "fwd" / "bwd" while a HIP graph of that pass is being captured
-    _staged = False       # ... the backward as one graph per block (a gradient hook runs between the replays)
-    _refreshed = False    # EncoderEngine: every weight copy was just rebuilt by _refresh_weights()
-
-    def _graph_init(self):
-        self.use_graphs = os.environ.get("PVRL_HIP_GRAPHS", "1") == "1"
-        self._capturing = None
-        self._graphs = {}
-        self._gpool = None
-        self._gkey = None
-        self._gseen = {}
-
-    def _graph_reset_host_state(self):
-        pass
-
-    def release_graphs(self):
-        """Drop every captured HIP graph of this engine (and give their memory pool back) WITH THE DEVICE IDLE -- call it, then
-        `gc.collect()`, before a long-lived process lets go of a model it has trained.  Round 6: with the MViT tests in front, the
-        train-loop tests aborted or hung inside the HIP runtime (ROCm 7.2, no message) in 3 of 4 runs: the dead models' ~20 captured
-        graphs and their pools were being torn down by Python's cyclic garbage collector at arbitrary points of the NEXT model's steps.
-        Releasing every test's GPU objects at a quiet point between tests (tests/conftest.py) removed it (5 of 5); doing the same from
-        a `__del__` did not (3 of 6 still failed: the collector still picks the moment), so there is no destructor hook."""
-        graphs = getattr(self, "_graphs", None)
-        if not graphs:
-            return
-        drop_graphs_quietly(graphs)
-        self._gkey = None
-        self._gpool = None
-
-    grad_hook_group = None      # optional: the hook for a list of blocks at once (distributed.GradReducer merges their all-reduces)
-
-    def _group_of(self, i, nb):
-        """-> (lo, hi): the blocks [lo, hi] whose gradient hook runs together with block i's (`hook_group` blocks per group: fewer,
-        larger collectives).  The LAST group of a backward -- blocks 0 .. hook_group - 1 -- runs per block (PVRL_HOOK_TAIL_SPLIT=0:
-        A/B): nothing is left to overlap its collective with but the embedding stage, so the exposed tail round stays one block's
-        ~45 MB instead of three blocks' ~135 MB."""
-        grp = max(1, int(getattr(self, "hook_group", 1)))
-        if i < grp and getattr(self, "hook_tail_split", True):
-            return i, i
-        lo = (i // grp) * grp
-        return lo, min(lo + grp, nb) - 1
-
-    def _run_hooks(self, blocks):
-        if not blocks or self.grad_hook is None:
-            return
-        if self.grad_hook_group is not None and len(blocks) > 1:
-            self.grad_hook_group(list(blocks))
-        else:
-            for j in blocks:
-                self.grad_hook(j)
-
-    def _bwd_group_end(self, state):
-        """staged backward: a group of blocks is done -- an engine that defers work of its blocks finishes it here (default: nothing)"""
-
-    def join_side_stream(self):
-        """Callers that drive a backward stage by stage call this before reading its results.  Every engine issues all of its
-        work on the current stream, so there is nothing to wait for."""
-
-    @staticmethod
-    def _saved_copy(saved):
-        """backward() consumes its `saved` dict (frees block entries as it goes): replays hand it a shallow copy"""
-        sv = dict(saved)
-        sv["blocks"] = list(saved["blocks"])
-        return sv
-
-    def _graph_forward(self, frames, training, save):
-        key = self._graph_key(frames, training, save)
-        g = self._graphs.get(key)
-        if g is None:
-            n = self._gseen.get(key, 0)
-            self._gseen[key] = n + 1
-            if n < self.GRAPH_WARMUP or len(self._graphs) >= self.GRAPH_MAX_KEYS:
-                self._gkey = None
-                return self._eager_forward(frames, training, save)
-            try:
-                g = self._capture_forward(key, frames, training, save)
-            except Exception as e:      # never fatal: the eager launch sequence is the same kernels
-                self._graph_failed("forward", e)
-                self._gkey = None
-                return self._eager_forward(frames, training, save)
-        g["frames"].copy_(frames)
-        g["fwd"].replay()
-        self.saved = g["saved"]
-        self._gkey = key if save else None
-        return g["feat"].clone()        # the graph's own output buffer is overwritten by the next replay
-
-    def _graph_failed(self, what, e):
-        import warnings
-        warnings.warn(f"HIP graph capture of the encoder {what} failed ({type(e).__name__}: {e}); continuing with eager "
-                      "launches")
-        self.use_graphs = False
-        self._capturing = None
-        self._graphs = {}
-        self._graph_reset_host_state()
-        torch.cuda.synchronize()
-
-    def _capture_forward(self, key, frames, training, save):
-        if self._gpool is None:
-            self._gpool = torch.cuda.graph_pool_handle()
-        st = torch.empty_like(frames)
-        st.copy_(frames)
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        self._capturing = "fwd"
-        try:
-            with torch.cuda.graph(graph, pool=self._gpool, capture_error_mode="thread_local"):
-                feat = self._eager_forward(st, training, save)
-        finally:
-            self._capturing = None
-        g = dict(fwd=graph, frames=st, feat=feat, saved=self.saved if save else None)
-        self._graphs[key] = g
-        return g
-
-    def _grads_fresh(self):
-        return all(p.grad is None for p in self._enc_params())
-
-    def _graph_backward(self, dfeat):
-        g = self._graphs[self._gkey]
-        staged_ok = hasattr(self, "_bwd_begin")
-        if not self._grads_fresh() or (self.grad_hook is not None and not staged_ok):
-            # accumulation into existing gradients (beta = 1 launches), or a hook this engine cannot stage: eager launches
-            self.saved = self._saved_copy(g["saved"])
-            self._gkey = None
-            return self._eager_backward(dfeat)
-        staged = self.grad_hook is not None             # cut the graph where the data-parallel reducer hooks in
-        nb = len(g["saved"]["blocks"])
-        slot = "bwd_staged" if staged else "bwd"
-        if g.get(slot) is None and not self._capture_backward(g, slot, staged, nb, dfeat):
-            self.saved = self._saved_copy(g["saved"])
-            self._gkey = None
-            return self._eager_backward(dfeat)
-        gb = g[slot]
-        gb["dfeat"].copy_(dfeat)
-        for p, v in gb["touched"]:      # before the hooks run: the reducer treats a parameter without .grad as unused
-            p.grad = v
-        for graph, blocks in gb["graphs"]:
-            graph.replay()
-            self._run_hooks(blocks)     # (staged: the blocks this graph finished, last block first)
-        self.saved = None
-        self._gkey = None
-
-    def _capture_backward(self, g, slot, staged, nb, dfeat):
-        """-> True when g[slot] holds the captured graph(s); False after a failed capture (graphs are then switched off)"""
-        st_in = torch.empty_like(dfeat.contiguous())
-        st_in.copy_(dfeat)
-        torch.cuda.synchronize()
-        hook, self.grad_hook = self.grad_hook, None
-        params = self._enc_params()
-        graphs = []
-        self._capturing = "bwd"
-        self._staged = staged          # the hook is detached while capturing: a stage must still finish its block's gradients itself
-        err = None
-        try:
-            self.saved = self._saved_copy(g["saved"])
-            if not staged:
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph, pool=self._gpool, capture_error_mode="thread_local"):
-                    self._eager_backward(st_in)
-                graphs.append((graph, []))
-            else:
-                # one graph per GROUP of `hook_group` blocks (the first also holds the final-norm stage, the last the embedding stage):
-                # the hook runs for a group's blocks after its replay
-                state = None
-                i = nb - 1
-                while i >= 0:
-                    lo = self._group_of(i, nb)[0]
-                    graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph, pool=self._gpool, capture_error_mode="thread_local"):
-                        if state is None:
-                            state = self._bwd_begin(st_in)
-                        for j in range(i, lo - 1, -1):
-                            self._bwd_block(state, j)
-                        self._bwd_group_end(state)
-                        if lo == 0:
-                            self._bwd_end(state)
-                    graphs.append((graph, list(range(i, lo - 1, -1))))
-                    i = lo - 1
-        except Exception as e:          # never fatal: the eager launch sequence is the same kernels
-            err = e
-        finally:
-            self._capturing = None
-            self._staged = False
-            self.grad_hook = hook
-        touched = [(p, p.grad) for p in params if p.grad is not None]     # all were None (_grads_fresh)
-        for p, _ in touched:            # capture ran no kernel: undo its host-side effect
-            p.grad = None
-        if err is not None:
-            self._graph_failed("backward", err)
-            return False
-        g[slot] = dict(graphs=graphs, dfeat=st_in, touched=touched)
-        return True
 
 
 class EncoderEngine(GraphReplay):

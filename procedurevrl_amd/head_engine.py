@@ -14,36 +14,27 @@ backward replay graphs captured from the plain kernel schedule below; parameter 
 gradient buffer like the encoder engines do.  The reference's random draws (mask_inds, pad_start, the noise tensors, the
 output permutation) are explicit INPUTS of the graphs, so pinned draws (parity tests) and fresh ones take the same path.
 """
-import os
-
 import torch
 
 from . import ops
 from .engine import SCALED_GRADS
+from .graphs import GraphCache, GraphOwner
 from .tfm_engine import StackEngine
 
 F32 = torch.float32
 
 
-class PretrainHeadEngine:
+class PretrainHeadEngine(GraphOwner):
     GRAPH_WARMUP = 2
     GRAPH_MAX_KEYS = 2
+    _cap = property(lambda self: self._capturing, lambda self, v: setattr(self, "_capturing", v))     # (the marker's name here)
 
     def __init__(self, owner):
         self.o = owner
-        self.use_graphs = os.environ.get("PVRL_HIP_GRAPHS", "1") == "1"
-        self._graphs, self._gseen = {}, {}
-        self._pool = None
-        self._cap = None
-        self._cap_seen = set()
-        self._gkey = None
+        self._cap_seen = set()      # the stack weights the running forward capture has re-cast (_wc)
+        self._gcache = GraphCache(self, "the pre-training head", self.GRAPH_WARMUP, self.GRAPH_MAX_KEYS)
         self.saved = None
         self._tconst = None
-
-    def release_graphs(self):       # (engine.GraphReplay.release_graphs)
-        from .engine import drop_graphs_quietly
-        drop_graphs_quietly(self._graphs)
-        self._gkey = None
 
     # ------------------------------------------------------------------ plumbing
     def params(self):
@@ -243,19 +234,10 @@ class PretrainHeadEngine:
             self._gkey = None
             return self._forward(feat, dr, save)
         key = self._key(feat)
-        g = self._graphs.get(key)
+        g = self._gcache.entry(key, lambda: self._capture_forward(feat, dr))
         if g is None:
-            k = self._gseen.get(key, 0)
-            self._gseen[key] = k + 1
-            if k < self.GRAPH_WARMUP or len(self._graphs) >= self.GRAPH_MAX_KEYS:
-                self._gkey = None
-                return self._forward(feat, dr, save)
-            try:
-                g = self._capture_forward(key, feat, dr)
-            except Exception as e:          # never fatal: the eager launch sequence is the same kernels
-                self._failed("forward", e)
-                self._gkey = None
-                return self._forward(feat, dr, save)
+            self._gkey = None
+            return self._forward(feat, dr, save)
         g["feat"].copy_(feat)
         for k in ("mask_inds", "pad_start", "noises", "rand_inds"):
             g["dr"][k].copy_(dr[k])
@@ -264,31 +246,15 @@ class PretrainHeadEngine:
         self._gkey = key
         return tuple(t.clone() for t in g["out"])       # the graph's own output buffers are overwritten by the next replay
 
-    def _failed(self, what, e):
-        import warnings
-        warnings.warn(f"HIP graph capture of the pre-training head {what} failed ({type(e).__name__}: {e}); continuing with "
-                      "eager launches")
-        self.use_graphs = False
-        self._cap = None
-        self._graphs = {}
-        torch.cuda.synchronize()
+    def _graph_reset_host_state(self):
+        self._cap_seen = set()
 
-    def _capture_forward(self, key, feat, dr):
-        if self._pool is None:
-            self._pool = torch.cuda.graph_pool_handle()
+    def _capture_forward(self, feat, dr):
         sf = feat.clone()
         sd = {k: v.clone() for k, v in dr.items()}
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        self._cap, self._cap_seen = "fwd", set()
-        try:
-            with torch.cuda.graph(graph, pool=self._pool, capture_error_mode="thread_local"):
-                out = self._forward(sf, sd, True)
-        finally:
-            self._cap = None
-        g = dict(fwd=graph, feat=sf, dr=sd, out=out, saved=self.saved, bwd=None)
-        self._graphs[key] = g
-        return g
+        self._cap_seen = set()
+        graph, out = self._gcache.capture("fwd", lambda: self._forward(sf, sd, True))
+        return dict(fwd=graph, feat=sf, dr=sd, out=out, saved=self.saved, bwd=None)
 
     def backward(self, d_pred, d_x0rep, d_inter):
         g = self._graphs.get(self._gkey) if self._gkey is not None else None
@@ -302,37 +268,25 @@ class PretrainHeadEngine:
         z = lambda t: torch.zeros(lvC, device=d_pred.device, dtype=F32) if t is None else t
         d_x0rep, d_inter = z(d_x0rep), z(d_inter)
         if g["bwd"] is None:
-            try:
-                sp, sx, si = d_pred.contiguous().clone(), d_x0rep.contiguous().clone(), d_inter.contiguous().clone()
-                torch.cuda.synchronize()
-                graph = torch.cuda.CUDAGraph()
-                saved = self.saved
-                self._cap = "bwd"
-                try:
-                    with torch.cuda.graph(graph, pool=self._pool, capture_error_mode="thread_local"):
-                        d_feat = self._backward(sp, sx, si)
-                finally:
-                    self._cap = None
-                touched = [(p, p.grad) for p in params if p.grad is not None]
-                for p, _ in touched:        # the capture ran no kernel: undo its host-side effect
-                    p.grad = None
-                g["bwd"] = dict(graph=graph, d_pred=sp, d_x0rep=sx, d_inter=si, d_feat=d_feat, touched=touched)
-                self.saved = saved
-            except Exception as e:
-                self._failed("backward", e)
-                for p in params:
-                    p.grad = None
+            g["bwd"] = self._gcache.attempt("backward", lambda: self._capture_backward(d_pred, d_x0rep, d_inter))
+            touched = self._gcache.take_grads(params)
+            if g["bwd"] is None:
                 self.saved = dict(g["saved"])
                 return self._backward(d_pred, d_x0rep, d_inter)
+            g["bwd"]["touched"] = touched
         gb = g["bwd"]
         gb["d_pred"].copy_(d_pred)
         gb["d_x0rep"].copy_(d_x0rep)
         gb["d_inter"].copy_(d_inter)
         gb["graph"].replay()
-        for p, v in gb["touched"]:
-            p.grad = v
+        self._gcache.install_grads(gb["touched"])
         self.saved = None
         return gb["d_feat"].clone()
+
+    def _capture_backward(self, d_pred, d_x0rep, d_inter):
+        sp, sx, si = d_pred.contiguous().clone(), d_x0rep.contiguous().clone(), d_inter.contiguous().clone()
+        graph, d_feat = self._gcache.capture("bwd", lambda: self._backward(sp, sx, si))
+        return dict(graph=graph, d_pred=sp, d_x0rep=sx, d_inter=si, d_feat=d_feat)
 
 
 class PretrainHeadFn(torch.autograd.Function):

@@ -9,7 +9,6 @@ attention kernels).  Every random draw of the reference forward (`mask_inds` :14
 them.
 """
 import math
-import os
 from collections import OrderedDict
 
 import torch
@@ -17,6 +16,7 @@ from torch import nn
 
 from . import ops
 from .functional import StackFn, gelu_f32, linear_f32
+from .graphs import GraphCache, GraphOwner
 
 
 class QuickGELU(nn.Module):
@@ -201,7 +201,7 @@ class DiffusionTransformer(nn.Module):
         return denoised
 
 
-class ClipTextModel(nn.Module):
+class ClipTextModel(nn.Module, GraphOwner):
     """The text half of openai/CLIP ViT-B/16 (third-party, un-vendored in the reference: `clip.load`,
     lib/models/vit.py:258-261).  Published architecture: 12 layers, width 512, 8 heads, context 77,
     vocab 49408, causal mask, ln_final, EOT-token (argmax id) pooling, text_projection.  Parameter
@@ -225,49 +225,35 @@ class ClipTextModel(nn.Module):
             nn.init.normal_(block.mlp.c_fc.weight, std=(2 * width) ** -0.5)
             nn.init.normal_(block.mlp.c_proj.weight, std=proj_std)
         nn.init.normal_(self.text_projection, std=width ** -0.5)
-        self.use_graphs = os.environ.get("PVRL_HIP_GRAPHS", "1") == "1"
-        self._graphs, self._gseen = {}, {}
+        # no shared pool: the tower is captured on the teacher's side stream (vit._teacher_begin) and must not share blocks with the
+        # main stream's graphs
+        self._gcache = GraphCache(self, "the text tower", shared_pool=False)
 
     def bind(self, owner):
         self._owner = [owner]
 
-    def release_graphs(self):       # (engine.GraphReplay.release_graphs)
-        from .engine import drop_graphs_quietly
-        drop_graphs_quietly(self._graphs)
-
     @torch.no_grad()
     def encode_text(self, text):
         """text int64 [n, 77] -> fp32 [n, embed_dim]; frozen, forward only.  The ~110 launches of the tower are replayed
-        from a HIP graph after two eager calls of a shape (same switch as the encoder: PVRL_HIP_GRAPHS=0 disables)."""
+        from a HIP graph of their own (graphs.GraphCache)."""
         if not (text.is_cuda and self.use_graphs):
             return self._encode_text(text)
         blk0 = self.transformer.resblocks[0]
         key = (tuple(text.shape), text.dtype, text.device.index, self.text_projection.data_ptr(),
                self.token_embedding.weight.data_ptr(), self.text_projection._version, blk0.attn.in_proj_weight._version,
                blk0.mlp.c_fc.weight._version)      # a checkpoint load (in-place copy) is a new key
-        g = self._graphs.get(key)
+        g = self._gcache.entry(key, lambda: self._capture_text(text))
         if g is None:
-            n = self._gseen.get(key, 0)
-            self._gseen[key] = n + 1
-            if n < 2 or len(self._graphs) >= 4:
-                return self._encode_text(text)
-            try:
-                st = text.clone()
-                torch.cuda.synchronize()
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                    out = self._encode_text(st)
-                g = self._graphs[key] = (graph, st, out)
-            except Exception as e:          # never fatal: the eager launches are the same kernels
-                import warnings
-                warnings.warn(f"HIP graph capture of the text tower failed ({type(e).__name__}: {e}); launching eagerly")
-                self.use_graphs = False
-                torch.cuda.synchronize()
-                return self._encode_text(text)
+            return self._encode_text(text)
         graph, st, out = g
         st.copy_(text)
         graph.replay()
         return out.clone()
+
+    def _capture_text(self, text):
+        st = text.clone()
+        graph, out = self._gcache.capture("fwd", lambda: self._encode_text(st))
+        return graph, st, out
 
     def _encode_text(self, text):
         from .tfm_engine import StackEngine
