@@ -3,7 +3,7 @@
 Same surface as the reference's `lib/models/build.py:8,17-54` (an fvcore `Registry` named MODEL whose
 entries are called as `obj(cfg)` and return an `nn.Module`).  Data parallelism differs by design: the
 reference wraps the module in `DistributedDataParallel(find_unused_parameters=True)` (build.py:49-53);
-here gradients live in one flat fp32 buffer (engine.GradStore) that `distributed.GradReducer`
+here gradients live in one flat fp32 buffer (grads.GradStore) that `distributed.GradReducer`
 all-reduces over RCCL in large chunks, so `build_model` returns the bare module for any NUM_GPUS.
 """
 import torch

@@ -4,7 +4,7 @@ API surface of the reference `lib/utils/distributed.py` (AllGather :13-29, all_g
 all_reduce :53-69, init_process_group :72-110, get_world_size / get_rank / is_master_proc ...), plus the
 data-parallel gradient reduction that replaces DDP (lib/models/build.py:49-53):
 
-  * gradients live in ONE flat fp32 buffer (engine.GradStore); `GradReducer` all-reduces it in
+  * gradients live in ONE flat fp32 buffer (grads.GradStore); `GradReducer` all-reduces it in
     per-block chunks (~28 MB each) launched as soon as a block's backward finishes, so the
     transfers overlap the remaining backward GEMMs; xGMI is point-to-point, so few large
     messages beat DDP's 25 MB bucket stream with per-bucket copies.

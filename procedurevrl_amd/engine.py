@@ -25,163 +25,12 @@ import torch
 
 from . import ops
 from ._lib import lib
-from .graphs import GraphReplay, drop_graphs_quietly      # (their home; imported from here by mvit.py and callers)
+from .grads import SCALED_GRADS, GradStore                # (re-exported: `from procedurevrl_amd.engine import GradStore` keeps working)
+from .graphs import GraphReplay, drop_graphs_quietly      # (their home; re-exported like the two above)
 from .transform import DecodedClips
 
 OP16 = ops.OP16
 F32 = torch.float32
-SCALED_GRADS = OP16 == torch.float16     # fp16-operand flavour: engines scale their internal gradients (GradStore.begin_scaled)
-
-
-class GradStore:
-    """Flat fp32 gradient buffer; every trainable parameter's .grad is a view into it so the
-    data-parallel all-reduce works on large contiguous chunks (reference: DDP buckets,
-    lib/models/build.py:49-53)."""
-
-    def __init__(self, named_params, device):
-        self.names = [n for n, _ in named_params]
-        self.params = [p for _, p in named_params]
-        sizes = [p.numel() for p in self.params]
-        # 64-element alignment keeps every view 256-byte aligned
-        self.offsets = []
-        off = 0
-        for s in sizes:
-            self.offsets.append(off)
-            off += (s + 63) // 64 * 64
-        self.end = off                     # end of the parameter gradients
-        # tail: one float per parameter, "this rank produced a gradient for it" -- summed over ranks inside the last
-        # chunk of the data-parallel all-reduce (distributed.GradReducer, DDP's find_unused_parameters bookkeeping) -- and one
-        # control slot behind them ("a rank asks for a re-synchronisation of the replicas", GradReducer find_unused="cached")
-        # ... and behind it `bad`, the optimiser's "skip this step" flag (csrc/optim.hip): raised on the device by the kernels that
-        # write parameter gradients when a value is inf / nan and by the training loop when a loss is; summed over ranks with the
-        # rest of the tail, so every replica drops the same step (misc.check_nan_losses, tools/train_net.py:174)
-        self.flat = torch.zeros(off + (len(sizes) + 2 + 63) // 64 * 64, device=device, dtype=F32)
-        self.used = self.flat[off:off + len(sizes)]
-        self.ctl = self.flat[off + len(sizes):off + len(sizes) + 1]
-        self.bad = self.flat[off + len(sizes) + 1:off + len(sizes) + 2]
-        self.fused_checked = set()     # parameters whose gradient producers raise `bad` themselves (target(..., fused=True))
-        self._unchecked = set()        # ... parameters with at least one writer that does not (target(..., checks=False))
-        self.reduced_over_ranks = False   # set by distributed.GradReducer.finish(): the buffer holds SUMS over ranks (the optimiser then scans all of it)
-        self.views = [self.flat[o:o + s].view(p.shape) for o, s, p in zip(self.offsets, sizes, self.params)]
-        self.index = {id(p): i for i, p in enumerate(self.params)}
-        self.scale = None       # fp16 flavour: device scalar S while an engine's backward runs with S-scaled gradients
-        self.inv = None         # ... and 1 / S: the `gscale` of the kernels that write parameter gradients (include/pvrl.h)
-        self._touched = []
-
-    def span(self, i):
-        """[a, b) of parameter i in the flat buffer, padding included"""
-        return self.offsets[i], (self.offsets[i + 1] if i + 1 < len(self.offsets) else self.end)
-
-    def target(self, p, fused=False, checks=True):
-        """-> (grad tensor to write into, beta).  beta = 0 overwrites, 1 accumulates.
-        `fused`: the caller's kernel computes  grad = beta * grad + self.inv * (its S-scaled result)  itself (`gscale`): nothing is
-        registered for unscale(), what is already there stays in true units.  `checks` (with `fused`): that kernel also raises `self.bad`
-        on a non-finite value it writes (`nonfinite`), so the optimiser's scan may skip the parameter (`fused_checked`); a writer that
-        takes no `nonfinite` argument says checks=False and its parameter stays in the scan."""
-        i = self.index[id(p)]
-        v = self.views[i]
-        if p.grad is None:
-            p.grad = v
-            t, beta = v, 0.0
-        elif p.grad.data_ptr() == v.data_ptr():
-            t, beta = v, 1.0
-        else:       # a foreign .grad tensor (someone else allocated it): accumulate into it
-            t, beta = p.grad, 1.0
-        if fused:
-            if not checks:                       # one unchecked writer is enough to keep the parameter in the scan, whatever the order
-                self._unchecked.add(i)
-                self.fused_checked.discard(i)
-            elif t is v and i not in self._unchecked:
-                self.fused_checked.add(i)
-            return t, beta
-        if self.scale is not None:
-            key = i if t is v else t
-            seen = self._seen_idx if t is v else self._seen_ptr
-            tag = i if t is v else t.data_ptr()
-            if tag not in seen:
-                seen.add(tag)
-                if beta == 1.0:
-                    t.mul_(self.scale)      # what is already there joins the S-scaled units until the engine is done
-            self._touched.append(key)
-        return t, beta
-
-    def prezero(self, params):
-        """An engine that is about to ACCUMULATE into every one of `params` (atomics / beta = 1 kernels): the ones without a
-        gradient yet get their zeroed view now, contiguous runs of the flat buffer in one fill each, instead of one small
-        fill per parameter at its first use.  Only for parameters the caller is certain to write: .grad stops being None."""
-        idx = sorted(self.index[id(p)] for p in params if p.grad is None and id(p) in self.index)
-        runs = []
-        for i in idx:
-            a, b = self.span(i)
-            if runs and runs[-1][1] == a:
-                runs[-1][1] = b
-            else:
-                runs.append([a, b])
-        for a, b in runs:
-            self.flat[a:b].zero_()
-        for i in idx:
-            self.params[i].grad = self.views[i]
-            if self.scale is not None:           # zeros need no conversion to S-scaled units, but are unscaled with the rest
-                self._seen_idx.add(i)
-                self._touched.append(i)
-
-    # ---- fp16-operand flavour: gradient scaling inside an engine's backward -------------------------------------------
-    # fp16 has 5 exponent bits: the 16-bit gradient operands of the backward GEMMs (rms 1e-6 .. 1e-4 at the benchmark
-    # shapes) would underflow.  An engine therefore multiplies the gradient it receives by a power of two S, chosen on the
-    # DEVICE from that gradient's magnitude (no host sync, capturable in a HIP graph), runs its whole backward in S-scaled
-    # units -- exact in fp32, and the 16-bit operands sit mid-range -- and multiplies every parameter gradient it produced
-    # by 1/S before anyone outside the engine sees it.  Nothing outside the engine ever holds a scaled value.
-    SCALE_TARGET = 256.0          # S * max|incoming gradient|; the largest internal operand stays ~100x below fp16's 65504
-
-    def begin_scaled(self, g):
-        """g: the fp32 gradient entering the engine -> g * S; registers S for target() / unscale()"""
-        # a non-finite incoming gradient (amax = inf / nan) must not turn S into 0 and 1/S into inf: S stays a finite power
-        # of two, so the non-finite values flow through to the loss check (train_epoch) instead of poisoning gradients
-        # accumulated by earlier micro-iterations
-        self._touched, self._seen_idx, self._seen_ptr = [], set(), set()
-        g = g.detach()
-        if g.is_cuda and g.dtype == F32 and g.is_contiguous() and g.numel() <= (1 << 20):      # one launch (csrc/optim.hip)
-            out = torch.empty_like(g)
-            self.scale = torch.empty(1, device=g.device, dtype=F32)
-            self.inv_row = torch.empty(4096, device=g.device, dtype=F32)       # 1 / S, also as a GEMM epilogue's per-row scale
-            self.inv = self.inv_row[:1]
-            lib().call("pvrl_grad_scale_begin", ops._ptr(g), g.numel(), float(self.SCALE_TARGET), ops._ptr(out), ops._ptr(self.scale),
-                       ops._ptr(self.inv_row), 4096, ops._stream())
-            return out
-        amax = torch.nan_to_num(g.abs().max(), nan=1.0, posinf=3e38).clamp(1e-30, 3e38)
-        self.scale = torch.exp2(torch.floor(torch.log2(self.SCALE_TARGET / amax)).clamp(-100.0, 100.0)).reshape(1)
-        self.inv = 1.0 / self.scale
-        self.inv_row = self.inv.expand(4096).contiguous()      # 1 / S as a GEMM epilogue's per-row scale (EncoderEngine._temporal_chain_all)
-        return g * self.scale
-
-    def unscale(self):
-        """multiply every gradient written since the last call by 1/S (contiguous runs of the flat buffer in one op each)"""
-        if self.scale is None or not self._touched:
-            return
-        inv = self.inv
-        idx = sorted(set(k for k in self._touched if isinstance(k, int)))
-        runs = []
-        for i in idx:
-            a, b = self.span(i)
-            if runs and runs[-1][1] == a:
-                runs[-1][1] = b
-            else:
-                runs.append([a, b])
-        for a, b in runs:
-            self.flat[a:b].mul_(inv)
-        done = set()
-        for k in self._touched:
-            if not isinstance(k, int) and k.data_ptr() not in done:
-                done.add(k.data_ptr())
-                k.mul_(inv)
-        self._touched = []
-
-    def end_scaled(self):
-        """-> 1/S (device scalar) for gradients the engine hands back to autograd (StackEngine's dx)"""
-        self.unscale()
-        inv = self.inv
-        self.scale = self.inv = None
-        return inv
 
 
 class _X:
@@ -408,18 +257,42 @@ class EncoderEngine(GraphReplay):
         if q:
             ops.gemm_tn_grouped(q, ws_tag="tn")
 
+    # every parameter gradient of a block is written by a kernel that takes the backward's scale out itself (`gscale` = 1 / S,
+    # fp16 flavour) and raises the optimiser's skip flag on a non-finite value (`nonfinite`): no pass over the gradient buffer
+    def _lin_wgrad(self, gs, dy, xin, lin, queue=True):
+        """the weight / bias gradient of the linear layer `lin` from dy^T xin: queued for the block's grouped launch, or
+        (queue=False) returned as an item for a launch of the caller's own"""
+        (dw, bw), (dbias, _) = gs.target(lin.weight, fused=True), gs.target(lin.bias, fused=True)
+        item = (dy, xin, dw, dbias, bw, gs.inv, gs.bad)
+        if not queue:
+            return item
+        self._wgrad(*item)
+
+    # (the 7-us reduces of the LayerNorm partials are deferred: one launch for the whole backward, or per group of blocks under a gradient hook)
+    def _lnbwd(self, gs, dh, x, st, ln, dx_in, dx_out, **sums):
+        """backward of the LayerNorm `ln` on the gradient stream (dx_out = dx_in + ...); `sums`: ops.layernorm_bwd's dxs / dxsum arguments"""
+        (dg, bg), (db, _) = gs.target(ln.weight, fused=True), gs.target(ln.bias, fused=True)
+        ops.layernorm_bwd(dh, x, st[0], st[1], ln.weight.detach(), dg, db, dx_in=dx_in, dx_out=dx_out, beta_acc=bg,
+                          gscale=gs.inv, nonfinite=gs.bad, defer=self._ln_defer, **sums)
+
     # ------------------------------------------------------------------ drop path
+    def _droppath_keep(self, device, training):
+        """-> (the blocks' DropPath rates, keep = 1 - rate as fp32 [nb, 1] on the device -- None when this pass draws nothing)"""
+        rates = [float(r) for r in self.m.drop_path_rates]
+        if not training or all(r == 0.0 for r in rates):
+            return rates, None
+        if self._keep is None or self._keep[0] != (tuple(rates), device):   # cached: a host->device copy blocks the host
+            self._keep = ((tuple(rates), device), torch.tensor([1.0 - r for r in rates], device=device, dtype=F32).view(len(rates), 1))
+        return rates, self._keep[1]
+
     def _droppath_all(self, B, N, T, device, training):
         """DropPath row scales of every block, lib/models/vit_utils.py:140-155: floor(keep + U[0,1)) / keep per dim-0 row
         of each branch (temporal: per (b h w); spatial: per (b t); mlp: per b).  All blocks are drawn and expanded to
         token rows with ONE set of launches (a per-block version costs ~20 tiny kernels x depth on the critical path)."""
-        rates = [float(r) for r in self.m.drop_path_rates]
+        rates, keep = self._droppath_keep(device, training)
         nb = len(rates)
-        if not training or all(r == 0.0 for r in rates):
+        if keep is None:
             return [None] * nb
-        if self._keep is None or self._keep[0] != (tuple(rates), device):   # cached: a host->device copy blocks the host
-            self._keep = ((tuple(rates), device), torch.tensor([1.0 - r for r in rates], device=device, dtype=F32).view(nb, 1))
-        keep = self._keep[1]
         n1, n2, n3 = B * N, B * T, B
         sc = torch.floor(keep + torch.rand((nb, n1 + n2 + n3), device=device)) / keep
         s1, s2, s3 = sc[:, :n1], sc[:, n1:n1 + n2], sc[:, n1 + n2:]
@@ -435,13 +308,10 @@ class EncoderEngine(GraphReplay):
     def _droppath_undivided(self, B, N, T, device, training):
         """DropPath of the undivided schemes: one draw per dim-0 sample and branch (vit.py:125-126 through vit_utils.py:140-155) -- per
         clip for `joint_space_time`, per (clip, frame) for `space_only`, whose pseudo-clips are the B here"""
-        rates = [float(r) for r in self.m.drop_path_rates]
+        rates, keep = self._droppath_keep(device, training)
         nb = len(rates)
-        if not training or all(r == 0.0 for r in rates):
+        if keep is None:
             return [None] * nb
-        if self._keep is None or self._keep[0] != (tuple(rates), device):
-            self._keep = ((tuple(rates), device), torch.tensor([1.0 - r for r in rates], device=device, dtype=F32).view(nb, 1))
-        keep = self._keep[1]
         sc = torch.floor(keep + torch.rand((nb, 2 * B), device=device)) / keep
         s2, s3 = sc[:, :B], sc[:, B:]
         s2_all = torch.cat([s2.repeat_interleave(N * T, dim=1), s2], 1)               # [nb, B*N*T + B]
@@ -574,6 +444,43 @@ class EncoderEngine(GraphReplay):
         L = lib()
         return L.PVRL_EPI_RESID_16 if self.resid16 else L.PVRL_EPI_RESID_F32
 
+    def _cls_mlp_fp32(self, blk, xc, s3c, out):
+        """out = xc + s3c * mlp(norm2(xc)) for the B cls rows in fp32 on the master weights (csrc/cls_chain.hip)"""
+        P = lambda t: t.detach()
+        hc, _, _ = ops.layernorm_fwd(xc, P(blk.norm2.weight), P(blk.norm2.bias), self.eps, out_dtype=F32, save_stats=False)
+        gc = ops.cls_linear(hc, P(blk.mlp.fc1.weight), P(blk.mlp.fc1.bias), gelu=True)
+        ops.cls_linear(gc, P(blk.mlp.fc2.weight), P(blk.mlp.fc2.bias), rowscale=s3c, biasscale=s3c, aux=xc, out=out)
+
+    def _mlp_fwd(self, blk, x, s3_all, sv, whole=False):
+        """x + s3 * mlp(norm2(x)) on every row (vit.py:155-157) -> (the next stage, h_m, (mean_m, rstd_m), u, g): what the block saves.
+        `whole`: the one-buffer fp32 stream of the divided path, fc2 as ONE GEMM over all rows"""
+        L = lib()
+        B, R = sv["B"], sv["R"]
+        P = lambda t: t.detach()
+        y = _X.new(R, B, self.C, x.c.device, sv["split"])
+        s3c = s3_all[R:] if s3_all is not None else None
+        h_m, mean_m, rstd_m = ops.layernorm_fwd(x.all(), P(blk.norm2.weight), P(blk.norm2.bias), self.eps)
+        u, g = ops.gemm_nt(h_m, self._weight(blk.mlp.fc1.weight).w, L.PVRL_EPI_GELU, bias=P(blk.mlp.fc1.bias))
+        w2 = self._weight(blk.mlp.fc2.weight).w
+        if whole:
+            ops.gemm_nt(g, w2, L.PVRL_EPI_RESID_F32, bias=P(blk.mlp.fc2.bias), rowscale=s3_all, aux=x.full, out0=y.full)
+        else:           # the patch rows with the stream's residual epilogue; the cls rows are the fp32 chain's below (or their own GEMM)
+            ops.gemm_nt(g[:R], w2, self._epi_resid(), bias=P(blk.mlp.fc2.bias), rowscale=s3_all[:R] if s3_all is not None else None,
+                        aux=x.p, out0=y.p)
+            if not self.cls_fp32:
+                ops.gemm_nt(g[R:], w2, L.PVRL_EPI_RESID_F32, bias=P(blk.mlp.fc2.bias), rowscale=s3c, aux=x.c, out0=y.c)
+        if self.cls_fp32:       # (the 16-bit path's cls rows of h_m / u / g stay what the backward reads; y's are replaced)
+            self._cls_mlp_fp32(blk, x.c, s3c, y.c)
+        return y, h_m, (mean_m, rstd_m), u, g
+
+    def _mlp_bwd(self, blk, s, dy, gs):
+        """backward of the MLP's two linear layers from dy = 16-bit(s3 * dx): queues their weight gradients -> dh, the gradient of norm2's output"""
+        L = lib()
+        self._lin_wgrad(gs, dy, s["g"], blk.mlp.fc2)
+        du = ops.gemm_nt(dy, self._weight(blk.mlp.fc2.weight).t, L.PVRL_EPI_DGELU, aux=s["u"])
+        self._lin_wgrad(gs, du, s["h_m"], blk.mlp.fc1)
+        return ops.gemm_nt(du, self._weight(blk.mlp.fc1.weight).t, L.PVRL_EPI_BF16)
+
     def _block_fwd(self, blk, x0, sv, dp, save, last=False):
         """`last`: the encoder's last block (with prune_last: the patch rows of x2 / x3 are neither computed nor defined)"""
         prune = last and self.prune_last
@@ -642,35 +549,22 @@ class EncoderEngine(GraphReplay):
             ops.group_reduce(pc, B, T, scale=s2_seq, alpha=1.0 / T, resid=x1.c, out=x2.c)
 
         # ---- MLP (vit.py:155-157) ----
-        x3 = _X.new(R, B, C, dev, split)
-        if prune:
-            self._undef(x3.p)
-        s3c = s3_all[R:] if s3_all is not None else None
-        w2 = self._weight(blk.mlp.fc2.weight).w
         if prune:
             # the B cls rows only; h_m / st_m / u / g are then [B, .] tensors (what the backward of this block reads, _block_bwd)
+            x3 = _X.new(R, B, C, dev, split)
+            self._undef(x3.p)
+            s3c = s3_all[R:] if s3_all is not None else None
             h_m = mean_m = rstd_m = u = g = None
             if save or not self.cls_fp32:
                 h_m, mean_m, rstd_m = ops.layernorm_fwd(x2.c, P(blk.norm2.weight), P(blk.norm2.bias), self.eps)
                 u, g = ops.gemm_nt(h_m, self._weight(blk.mlp.fc1.weight).w, L.PVRL_EPI_GELU, bias=P(blk.mlp.fc1.bias))
-            if not self.cls_fp32:
-                ops.gemm_nt(g, w2, L.PVRL_EPI_RESID_F32, bias=P(blk.mlp.fc2.bias), rowscale=s3c, aux=x2.c, out0=x3.c)
-        else:
-            h_m, mean_m, rstd_m = ops.layernorm_fwd(x2.all(), P(blk.norm2.weight), P(blk.norm2.bias), self.eps)
-            u, g = ops.gemm_nt(h_m, self._weight(blk.mlp.fc1.weight).w, L.PVRL_EPI_GELU, bias=P(blk.mlp.fc1.bias))
-            if split:       # the patch rows with the 16-bit residual epilogue; the cls rows are the fp32 chain's below (or their own GEMM)
-                ops.gemm_nt(g[:R], w2, epi_res, bias=P(blk.mlp.fc2.bias), rowscale=s3_all[:R] if s3_all is not None else None,
-                            aux=x2.p, out0=x3.p)
-                if not self.cls_fp32:
-                    ops.gemm_nt(g[R:], w2, L.PVRL_EPI_RESID_F32, bias=P(blk.mlp.fc2.bias), rowscale=s3c, aux=x2.c, out0=x3.c)
+            if self.cls_fp32:
+                self._cls_mlp_fp32(blk, x2.c, s3c, x3.c)
             else:
-                ops.gemm_nt(g, w2, L.PVRL_EPI_RESID_F32, bias=P(blk.mlp.fc2.bias), rowscale=s3_all, aux=x2.full, out0=x3.full)
-        if self.cls_fp32:       # (the 16-bit path's cls rows of h_m / u / g stay what the backward reads; x3's are replaced)
-            hc, _, _ = ops.layernorm_fwd(x2.c, P(blk.norm2.weight), P(blk.norm2.bias), self.eps, out_dtype=F32,
-                                         save_stats=False)
-            gc = ops.cls_linear(hc, P(blk.mlp.fc1.weight), P(blk.mlp.fc1.bias), gelu=True)
-            ops.cls_linear(gc, P(blk.mlp.fc2.weight), P(blk.mlp.fc2.bias), rowscale=s3c, biasscale=s3c, aux=x2.c,
-                           out=x3.c)
+                ops.gemm_nt(g, self._weight(blk.mlp.fc2.weight).w, L.PVRL_EPI_RESID_F32, bias=P(blk.mlp.fc2.bias), rowscale=s3c,
+                            aux=x2.c, out0=x3.c)
+        else:
+            x3, h_m, (mean_m, rstd_m), u, g = self._mlp_fwd(blk, x2, s3_all, sv, whole=not split)
         if save:
             sv["blocks"].append(dict(x0=x0, x1=x1, x2=x2, h_t=h_t, st_t=(mean_t, rstd_t), qkv_t=qkv_t, o_t=o_t,
                                      lse_t=lse_t, h_s=h_s, st_s=(mean_s, rstd_s), qkv_s=qkv_s, o_s=o_s,
@@ -694,7 +588,6 @@ class EncoderEngine(GraphReplay):
         dev = x0.c.device
         split, epi_res = sv["split"], self._epi_resid()
         s2_all = dp["s2_all"] if dp else None
-        s3_all = dp["s3_all"] if dp else None
         row = lambda s, a, b: s[a:b] if s is not None else None
         P = lambda t: t.detach()
 
@@ -713,21 +606,10 @@ class EncoderEngine(GraphReplay):
             ops.gemm_nt(o_s[R:], wproj, L.PVRL_EPI_RESID_F32, bias=P(blk.attn.proj.bias), rowscale=row(s2_all, R, M), aux=x0.c, out0=x1.c)
 
         # ---- MLP ----
-        x2 = _X.new(R, B, C, dev, split)
-        h_m, mean_m, rstd_m = ops.layernorm_fwd(x1.all(), P(blk.norm2.weight), P(blk.norm2.bias), self.eps)
-        u, g = ops.gemm_nt(h_m, self._weight(blk.mlp.fc1.weight).w, L.PVRL_EPI_GELU, bias=P(blk.mlp.fc1.bias))
-        w2 = self._weight(blk.mlp.fc2.weight).w
-        ops.gemm_nt(g[:R], w2, epi_res, bias=P(blk.mlp.fc2.bias), rowscale=row(s3_all, 0, R), aux=x1.p, out0=x2.p)
-        if self.cls_fp32:       # (the 16-bit cls rows of h_m / u / g stay what the backward reads)
-            hc, _, _ = ops.layernorm_fwd(x1.c, P(blk.norm2.weight), P(blk.norm2.bias), self.eps, out_dtype=F32, save_stats=False)
-            gc = ops.cls_linear(hc, P(blk.mlp.fc1.weight), P(blk.mlp.fc1.bias), gelu=True)
-            ops.cls_linear(gc, P(blk.mlp.fc2.weight), P(blk.mlp.fc2.bias), rowscale=row(s3_all, R, M), biasscale=row(s3_all, R, M),
-                           aux=x1.c, out=x2.c)
-        else:
-            ops.gemm_nt(g[R:], w2, L.PVRL_EPI_RESID_F32, bias=P(blk.mlp.fc2.bias), rowscale=row(s3_all, R, M), aux=x1.c, out0=x2.c)
+        x2, h_m, st_m, u, g = self._mlp_fwd(blk, x1, dp["s3_all"] if dp else None, sv)
         if save:
             sv["blocks"].append(dict(undivided=True, x0=x0, x1=x1, h_s=h_s, st_s=(mean_s, rstd_s), qkv_s=qkv_s, o_s=o_s, lse_s=lse_s,
-                                     h_m=h_m, st_m=(mean_m, rstd_m), u=u, g=g, dp=dp))
+                                     h_m=h_m, st_m=st_m, u=u, g=g, dp=dp))
         return x2
 
     def _block_bwd_undivided(self, blk, s, sv, dx, gs, dy, has_prev, prev_dp):
@@ -740,30 +622,16 @@ class EncoderEngine(GraphReplay):
         dp = s["dp"]
         s2_all = dp["s2_all"] if dp else None
         row = lambda v, a, b: v[a:b] if v is not None else None
-        P = lambda t: t.detach()
-        defer = self._ln_defer
-
-        def wgrad(d, xin, lin):
-            (dw, bw), (dbias, _) = gs.target(lin.weight, fused=True), gs.target(lin.bias, fused=True)
-            self._wgrad(d, xin, dw, dbias, bw, gscale=gs.inv, nonfinite=gs.bad)
-
-        def lnbwd(dh, x, st, ln, dxs, dxs_scale):
-            (dg, bg), (db, _) = gs.target(ln.weight, fused=True), gs.target(ln.bias, fused=True)
-            ops.layernorm_bwd(dh, x, st[0], st[1], P(ln.weight), dg, db, dx_in=dx.all(), dx_out=dx.all(), beta_acc=bg,
-                              dxs=dxs, dxs_scale=dxs_scale, gscale=gs.inv, nonfinite=gs.bad, defer=defer)
 
         # ---- MLP ----
-        wgrad(dy, s["g"], blk.mlp.fc2)
-        du = ops.gemm_nt(dy, self._weight(blk.mlp.fc2.weight).t, L.PVRL_EPI_DGELU, aux=s["u"])
-        wgrad(du, s["h_m"], blk.mlp.fc1)
-        dh = ops.gemm_nt(du, self._weight(blk.mlp.fc1.weight).t, L.PVRL_EPI_BF16)
-        del du
+        dh = self._mlp_bwd(blk, s, dy, gs)
         dps = torch.empty((M, C), device=dev, dtype=OP16)
-        lnbwd(dh, s["x1"].all(), s["st_m"], blk.norm2, dps[:R], row(s2_all, 0, R))       # also emits 16-bit(s2 * dx[:R])
+        self._lnbwd(gs, dh, s["x1"].all(), s["st_m"], blk.norm2, dx.all(), dx.all(), dxs=dps[:R],
+                    dxs_scale=row(s2_all, 0, R))       # also emits 16-bit(s2 * dx[:R])
         ops.cast_scale(dx.c, row(s2_all, R, M), out=dps[R:])
 
         # ---- attention ----
-        wgrad(dps, s["o_s"], blk.attn.proj)
+        self._lin_wgrad(gs, dps, s["o_s"], blk.attn.proj)
         do = ops.gemm_nt(dps, self._weight(blk.attn.proj.weight).t, L.PVRL_EPI_BF16)
         del dps
         S = N * T + 1
@@ -771,12 +639,12 @@ class EncoderEngine(GraphReplay):
         bwd = ops.attn_long_bwd if ops.attn_uses_long(S) else ops.attn_bwd
         bwd(s["qkv_s"], s["o_s"][:R], s["o_s"][R:], do[:R], do[R:], s["lse_s"], B, S, H, self.scale, mode=1, T=1, cls_base=R,
             dqkv=dqkv, dqkv_cls=dqkv[R:])
-        wgrad(dqkv, s["h_s"], blk.attn.qkv)
+        self._lin_wgrad(gs, dqkv, s["h_s"], blk.attn.qkv)
         dh = ops.gemm_nt(dqkv, self._weight(blk.attn.qkv.weight).t, L.PVRL_EPI_BF16)
         del dqkv, do
         s3p = prev_dp["s3_all"] if (has_prev and prev_dp) else None
         dy_next = torch.empty((M if has_prev else R, C), device=dev, dtype=OP16)
-        lnbwd(dh, s["x0"].all(), s["st_s"], blk.norm1, dy_next[:R], row(s3p, 0, R))
+        self._lnbwd(gs, dh, s["x0"].all(), s["st_s"], blk.norm1, dx.all(), dx.all(), dxs=dy_next[:R], dxs_scale=row(s3p, 0, R))
         if has_prev:
             ops.cast_scale(dx.c, row(s3p, R, M), out=dy_next[R:])
         self.flush_wgrads()
@@ -896,29 +764,22 @@ class EncoderEngine(GraphReplay):
         if gs.inv is not None:       # the three small embedding gradients below are sums of these: the scale is taken out here
             G = G * gs.inv           # (a non-finite value in dx reaches the patch-embed weight gradient above, which raises gs.bad)
             dcls_rows = dcls_rows * gs.inv
-        self._acc(gs, m.cls_token, dcls_rows.view(1, 1, C))
+        # (the three are in true units already, and torch's copy_ / add_ raise no flag: fused, checks=False)
+        gs.accumulate(m.cls_token, dcls_rows.view(1, 1, C), fused=True, checks=False)
         dpos = torch.cat([dcls_rows.unsqueeze(0), G.sum(1)], 0)
         dtime = G.sum(0)
         pos_p, tim_p = m.pos_embed, None if self.space_only else m.time_embed
         if pos_p.shape[1] != N + 1 or (tim_p is not None and tim_p.shape[1] != T):
             raise NotImplementedError("training with resized pos/time embeddings is not supported (reference "
                                       "resizes at inference only, vit.py:374)")
-        self._acc(gs, pos_p, dpos.unsqueeze(0))
+        gs.accumulate(pos_p, dpos.unsqueeze(0), fused=True, checks=False)
         if tim_p is not None:
-            self._acc(gs, tim_p, dtime.unsqueeze(0))
+            gs.accumulate(tim_p, dtime.unsqueeze(0), fused=True, checks=False)
         self.flush_wgrads()
         self._finish_deferred(gs)
         if gs.scale is not None:
             gs.end_scaled()
         self.saved = None
-
-    @staticmethod
-    def _acc(gs, p, g):
-        tgt, beta = gs.target(p, fused=True, checks=False)      # (g is in true units already; see _bwd_end.  torch copy_ / add_: no flag raised)
-        if beta == 0.0:
-            tgt.copy_(g.view_as(tgt))
-        else:
-            tgt.add_(g.view_as(tgt))
 
     def _block_bwd(self, blk, s, sv, dx, gs, dy, has_prev, prev_dp, dxp_zero=False):
         L = lib()
@@ -932,38 +793,19 @@ class EncoderEngine(GraphReplay):
         s2_seq = dp["s2_seq"] if dp else None
         s2_tok = dp["s2_tok"] if dp else None
         s3_all = dp["s3_all"] if dp else None
-        P = lambda t: t.detach()
-
-        # every parameter gradient of the block is written by a kernel that takes the backward's scale out itself (`gscale` = 1 / S,
-        # fp16 flavour) and raises the optimiser's skip flag on a non-finite value (`nonfinite`): no pass over the gradient buffer
-        def wgrad(dy, xin, lin):
-            (dw, bw), (dbias, _) = gs.target(lin.weight, fused=True), gs.target(lin.bias, fused=True)
-            self._wgrad(dy, xin, dw, dbias, bw, gscale=gs.inv, nonfinite=gs.bad)
-
-        # (the 7-us reduces of the LayerNorm partials are deferred: one launch for the whole backward, or per group of blocks under a gradient hook)
-        defer = self._ln_defer
-
-        def lnbwd(dh, x, st, ln, dx_in, dx_out, dxs=None, dxs_scale=None, dxsum=None, dxsum_beta=None):
-            (dg, bg), (db, _) = gs.target(ln.weight, fused=True), gs.target(ln.bias, fused=True)
-            ops.layernorm_bwd(dh, x, st[0], st[1], P(ln.weight), dg, db, dx_in=dx_in, dx_out=dx_out, beta_acc=bg,
-                              dxs=dxs, dxs_scale=dxs_scale, dxsum=dxsum, dxsum_beta=dxsum_beta, gscale=gs.inv, nonfinite=gs.bad,
-                              defer=defer)
 
         if s.get("pruned"):
             # The encoder's last block under prune_last: dx is zero outside the B cls rows (only `x[:, 0]` of the final norm is read,
             # vit.py:418-421), so the MLP, norm2 and the spatial projection back-propagate those rows alone: dy, h_m, u, g are [B, .]
             # tensors here, the weight gradients sums over B (B * T for the projection) rows -- their own small grouped launch: in the
             # block's grouped launch they would force ONE row slice on its 50k-row problems.
-            def wgrad_c(d, xin, lin):
-                (dw, bw), (dbias, _) = gs.target(lin.weight, fused=True), gs.target(lin.bias, fused=True)
-                return (d, xin, dw, dbias, bw, gs.inv, gs.bad)
-            wq = [wgrad_c(dy, s["g"], blk.mlp.fc2)]
+            wq = [self._lin_wgrad(gs, dy, s["g"], blk.mlp.fc2, queue=False)]
             du = ops.gemm_nt(dy, self._weight(blk.mlp.fc2.weight).t, L.PVRL_EPI_DGELU, aux=s["u"])
-            wq.append(wgrad_c(du, s["h_m"], blk.mlp.fc1))
+            wq.append(self._lin_wgrad(gs, du, s["h_m"], blk.mlp.fc1, queue=False))
             dh = ops.gemm_nt(du, self._weight(blk.mlp.fc1.weight).t, L.PVRL_EPI_BF16)
-            lnbwd(dh, s["x2"].c, s["st_m"], blk.norm2, dx.c, dx.c)
+            self._lnbwd(gs, dh, s["x2"].c, s["st_m"], blk.norm2, dx.c, dx.c)
             dpc = ops.group_bcast(dx.c, B, T, scale=s2_seq, alpha=1.0 / T)
-            wq.append(wgrad_c(dpc, s["o_s"][R:], blk.attn.proj))
+            wq.append(self._lin_wgrad(gs, dpc, s["o_s"][R:], blk.attn.proj, queue=False))
             if not s.get("cls_attn"):
                 ops.gemm_tn_grouped(wq, ws_tag="tn_cls")
             if s.get("cls_attn"):
@@ -974,17 +816,13 @@ class EncoderEngine(GraphReplay):
             del du, dpc
         else:
             # ---- MLP ----   (dy = bf16(s3 * dx) arrives from the caller)
-            wgrad(dy, s["g"], blk.mlp.fc2)
-            du = ops.gemm_nt(dy, self._weight(blk.mlp.fc2.weight).t, L.PVRL_EPI_DGELU, aux=s["u"])
-            wgrad(du, s["h_m"], blk.mlp.fc1)
-            dh = ops.gemm_nt(du, self._weight(blk.mlp.fc1.weight).t, L.PVRL_EPI_BF16)
-            del du
+            dh = self._mlp_bwd(blk, s, dy, gs)
             dps = torch.empty((R + B * T, C), device=dev, dtype=OP16)
-            lnbwd(dh, s["x2"].all(), s["st_m"], blk.norm2, dx.all(), dx.all(), dxs=dps[:R], dxs_scale=s2_tok)   # also emits bf16(s2 * dx[:R])
+            self._lnbwd(gs, dh, s["x2"].all(), s["st_m"], blk.norm2, dx.all(), dx.all(), dxs=dps[:R], dxs_scale=s2_tok)   # also emits bf16(s2 * dx[:R])
 
             # ---- spatial ----
             ops.group_bcast(dx.c, B, T, scale=s2_seq, alpha=1.0 / T, out=dps[R:])
-            wgrad(dps, s["o_s"], blk.attn.proj)
+            self._lin_wgrad(gs, dps, s["o_s"], blk.attn.proj)
             do = ops.gemm_nt(dps, self._weight(blk.attn.proj.weight).t, L.PVRL_EPI_BF16)
             del dps
         dqkv = torch.empty((M + B * T, 3 * C), device=dev, dtype=OP16)
@@ -1009,14 +847,14 @@ class EncoderEngine(GraphReplay):
             ops.attn_bwd(s["qkv_s"], s["o_s"][:R], s["o_s"][R:], do[:R], do[R:], s["lse_s"], B * T, N + 1, H, self.scale,
                          mode=1, T=T, cls_base=R, dqkv=dqkv[:M], dqkv_cls=dqkv[M:])
             ops.group_reduce(dqkv[M:], B, T, out=dqkv[R:M])
-            wgrad(dqkv[:M], s["h_s"], blk.attn.qkv)
+            self._lin_wgrad(gs, dqkv[:M], s["h_s"], blk.attn.qkv)
             dh = ops.gemm_nt(dqkv[:M], self._weight(blk.attn.qkv.weight).t, L.PVRL_EPI_BF16)
         del dqkv, do
         # also emits dz = bf16(s1 * dx[:R]) and, into temporal_fc.bias.grad, the unscaled column sums of dx[:R]
         dz = torch.empty((R, C), device=dev, dtype=OP16)
         dbf, bbf = gs.target(blk.temporal_fc.bias, fused=True)
-        lnbwd(dh, s["x1"].all(), s["st_s"], blk.norm1, dx.all(p_zero=dxp_zero), dx.all(), dxs=dz, dxs_scale=s1_tok, dxsum=dbf,
-              dxsum_beta=bbf)
+        self._lnbwd(gs, dh, s["x1"].all(), s["st_s"], blk.norm1, dx.all(p_zero=dxp_zero), dx.all(), dxs=dz, dxs_scale=s1_tok, dxsum=dbf,
+                    dxsum_beta=bbf)
 
         # ---- temporal (rows [0, R); cls rows pass straight through): proj + temporal_fc as ONE map W_e (_fused_temporal)
         fe = self._fused_temporal(blk)
@@ -1029,13 +867,13 @@ class EncoderEngine(GraphReplay):
             dqkv_t = ops.attn_t8_bwd(s["qkv_t"], dot, B * N, H, self.scale)
         else:
             dqkv_t, _ = ops.attn_bwd(s["qkv_t"], s["o_t"], None, dot, None, s["lse_t"], B * N, T, H, self.scale, mode=0)
-        wgrad(dqkv_t, s["h_t"], blk.temporal_attn.qkv)
+        self._lin_wgrad(gs, dqkv_t, s["h_t"], blk.temporal_attn.qkv)
         dh = ops.gemm_nt(dqkv_t, self._weight(blk.temporal_attn.qkv.weight).t, L.PVRL_EPI_BF16)
         # the block's input gradient is final after this kernel: it also emits the bf16 operand of the next stage
         # (previous block's MLP backward with that block's DropPath scale, or the patch-embed weight gradient)
         s3p = prev_dp["s3_all"] if (has_prev and prev_dp) else None
         dy_next = torch.empty((M if has_prev else R, C), device=dev, dtype=OP16)
-        lnbwd(dh, s["x0"].patch(), s["st_t"], blk.temporal_norm1, dx.patch(), dx.patch(), dxs=dy_next[:R], dxs_scale=s3p)
+        self._lnbwd(gs, dh, s["x0"].patch(), s["st_t"], blk.temporal_norm1, dx.patch(), dx.patch(), dxs=dy_next[:R], dxs_scale=s3p)
         if has_prev:
             ops.cast_scale(dx.c, s3p[R:] if s3p is not None else None, out=dy_next[R:])
         self.flush_wgrads()

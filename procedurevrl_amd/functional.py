@@ -4,11 +4,12 @@ PyTorch's autograd is used only to connect the pieces in the order the reference
 (lib/models/vit.py:283-352, tools/train_net.py:147-181); no Function computes with ATen kernels
 except for trivial shape plumbing (transposes of <1 MB operands, bias column sums).
 Parameter gradients of the kernel-scheduled stacks are written straight into the model's flat
-gradient buffer (engine.GradStore); the Functions return None for them.
+gradient buffer (grads.GradStore); the Functions return None for them.
 """
 import torch
 
 from . import ops
+from .grads import SCALED_GRADS
 
 F32 = torch.float32
 
@@ -46,7 +47,6 @@ class StackFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        from .engine import SCALED_GRADS
         gs = ctx.owner_ref.grad_store() if SCALED_GRADS else None
         if gs is not None:
             dy = gs.begin_scaled(dy)                 # fp16-operand flavour: the stack's backward runs in S-scaled units

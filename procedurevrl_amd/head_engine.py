@@ -17,7 +17,7 @@ output permutation) are explicit INPUTS of the graphs, so pinned draws (parity t
 import torch
 
 from . import ops
-from .engine import SCALED_GRADS
+from .grads import SCALED_GRADS
 from .graphs import GraphCache, GraphOwner
 from .tfm_engine import StackEngine
 
@@ -202,11 +202,7 @@ class PretrainHeadEngine(GraphOwner):
         for p, g in grads:
             if not p.requires_grad:
                 continue
-            t, beta = gs.target(p)
-            if beta == 0.0:
-                t.copy_(g.view_as(t))
-            else:
-                t.add_(g.view_as(t))
+            gs.accumulate(p, g)
         self.saved = None
         return d_feat
 

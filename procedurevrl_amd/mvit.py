@@ -21,7 +21,8 @@ from . import ops
 from . import ops_mvit as om
 from ._lib import lib
 from .build import MODEL_REGISTRY
-from .engine import GradStore, GraphReplay
+from .grads import SCALED_GRADS, GradStore
+from .graphs import GraphReplay
 from .weights import WeightCache
 from .vit import VisionTransformer as _StepMatchingModel, trunc_normal_
 
@@ -214,7 +215,7 @@ class MViT_encoder(nn.Module):
 class MViTEngine(GraphReplay):
     """Kernel schedule of MViT_encoder.forward (slowfast_mvit/mvit.py:346-407) and its hand-written backward.
     Token matrices are fp32 [B*L + B, pad128(C)]: patch tokens (b, t, h, w) first, the B cls tokens last.
-    The ~3,000 launches of a step are replayed from HIP graphs (engine.GraphReplay; with a data-parallel gradient hook
+    The ~3,000 launches of a step are replayed from HIP graphs (graphs.GraphReplay; with a data-parallel gradient hook
     installed the backward is one graph per block, the hook running between them)."""
 
     def __init__(self, owner, enc):
@@ -229,7 +230,7 @@ class MViTEngine(GraphReplay):
         self.prune_last = os.environ.get("PVRL_PRUNE_LAST", "1") == "1"
         self._graph_init()
 
-    # -------------------------------------------------------------- HIP graphs (engine.GraphReplay)
+    # -------------------------------------------------------------- HIP graphs (graphs.GraphReplay)
     def _eager_forward(self, frames, training, save):
         return self._forward(frames, training, save, None)
 
@@ -395,7 +396,7 @@ class MViTEngine(GraphReplay):
         return x2
 
     # -------------------------------------------------------------- backward
-    # The backward in three kinds of stages -- begin (final norm), one per block, end (stem) -- so that engine.GraphReplay can
+    # The backward in three kinds of stages -- begin (final norm), one per block, end (stem) -- so that graphs.GraphReplay can
     # capture one HIP graph per block and run the data-parallel reducer's hook between them (staged capture); without a
     # hook the whole backward is one graph.
     def _bwd_begin(self, dfeat):
@@ -409,7 +410,6 @@ class MViTEngine(GraphReplay):
         Cl = enc.plan[-1]["dim_out"]
         Rl = xf.shape[0] - B
         dx = torch.zeros_like(xf)
-        from .engine import SCALED_GRADS
         gs = self.m.grad_store() if SCALED_GRADS else None
         if gs is not None:
             dfeat = gs.begin_scaled(dfeat.float())     # fp16-operand flavour: backward in S-scaled units (GradStore.begin_scaled)

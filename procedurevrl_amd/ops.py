@@ -335,57 +335,24 @@ def layernorm_fwd(x, gamma, beta, eps, out_dtype=OP16, out=None, save_stats=True
 
 def layernorm_bwd(dy, x, mean, rstd, gamma, dgamma, dbeta, dx_in=None, dx_out=None, beta_acc=0.0, dxs=None, dxs_scale=None,
                   dxsum=None, dxsum_beta=None, gscale=None, nonfinite=None, defer=None):
-    """`dxs` (optional bf16 [rows <= M, C]) additionally receives bf16(dxs_scale[m] * dx_out[m]); `dxsum` (optional fp32
+    """`x`: fp32 [M, C] (pvrl_layernorm_bwd), or a SplitRows (pvrl_layernorm_bwd_split): dx_in (optional; a None part reads as zeros)
+    and dx_out are then SplitRows with the same split.
+    `dxs` (optional bf16 [rows <= M, C]) additionally receives bf16(dxs_scale[m] * dx_out[m]); `dxsum` (optional fp32
     [C]) the unscaled column sums of those rows of dx_out (dxsum = dxsum_beta * dxsum + sums).
     `defer` (a list): the per-workgroup partial sums of dgamma / dbeta / dxsum stay in a private workspace and an entry is appended
     for `layernorm_bwd_reduce_batched`, which reduces many LayerNorms' partials in one launch."""
     L = lib()
-    if isinstance(x, SplitRows):
-        return _layernorm_bwd_split(dy, x, mean, rstd, gamma, dgamma, dbeta, dx_in, dx_out, beta_acc, dxs, dxs_scale, dxsum,
-                                    dxsum_beta, gscale, nonfinite, defer)
-    _chk2d(dy); _chk2d(x, F32)
-    M, C = x.shape
-    if dx_out is None:
-        dx_out = torch.empty((M, C), device=x.device, dtype=F32)
-    nbytes = L.call("pvrl_layernorm_bwd_workspace_bytes", M, C)
-    if defer is not None:
-        ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
-        assert dxsum is None or dxs is not None
-        L.call("pvrl_layernorm_bwd", _ptr(dy), _ld(dy), 1 if dy.dtype == F32 else 0, _ptr(x), _ld(x), _ptr(mean),
-               _ptr(rstd), _ptr(gamma), _ptr(dx_in), _ld(dx_in) if dx_in is not None else 0, _ptr(dx_out), _ld(dx_out),
-               float(beta_acc), None, None, _ptr(ws), ws.numel(), M, C, _ptr(dxs), _ld(dxs) if dxs is not None else 0,
-               _ptr(dxs_scale), dxs.shape[0] if dxs is not None else 0, _ptr(dxsum), None, None, _stream())
-        defer.append(dict(part=ws, M=M, C=C, beta=float(beta_acc), beta_sum=float(beta_acc if dxsum_beta is None else dxsum_beta),
-                          dgamma=dgamma, dbeta=dbeta, dxsum=dxsum))
-        return dx_out
-    ws = workspace(nbytes, x.device, "ln")
-    tgt = dxsum
-    if dxsum is not None:
-        assert dxs is not None and dxsum.dtype == F32 and dxsum.is_contiguous() and dxsum.numel() == C
-        if (beta_acc if dxsum_beta is None else dxsum_beta) != beta_acc:      # the kernel has one beta for all three sums
-            tgt = torch.empty_like(dxsum)
-    L.call("pvrl_layernorm_bwd", _ptr(dy), _ld(dy), 1 if dy.dtype == F32 else 0, _ptr(x), _ld(x), _ptr(mean),
-           _ptr(rstd), _ptr(gamma), _ptr(dx_in), _ld(dx_in) if dx_in is not None else 0, _ptr(dx_out), _ld(dx_out),
-           float(beta_acc), _ptr(dgamma), _ptr(dbeta), _ptr(ws), ws.numel(), M, C, _ptr(dxs),
-           _ld(dxs) if dxs is not None else 0, _ptr(dxs_scale), dxs.shape[0] if dxs is not None else 0, _ptr(tgt),
-           _ptr(gscale), _ptr(nonfinite), _stream())
-    if tgt is not dxsum:
-        if beta_acc != 0.0:
-            raise PvrlError("layernorm_bwd: dxsum_beta = 0 with beta_acc != 0 is not supported")
-        dxsum.mul_(float(dxsum_beta)).add_(tgt)
-    return dx_out
-
-
-def _layernorm_bwd_split(dy, x, mean, rstd, gamma, dgamma, dbeta, dx_in, dx_out, beta_acc, dxs, dxs_scale, dxsum, dxsum_beta,
-                         gscale, nonfinite, defer):
-    """layernorm_bwd over a split matrix (pvrl_layernorm_bwd_split): x, dx_in (optional; a None part reads as zeros) and dx_out are
-    SplitRows with the same split"""
-    L = lib()
+    split = isinstance(x, SplitRows)
     _chk2d(dy)
     M, C = x.shape
-    assert isinstance(dx_out, SplitRows) and dx_out.n_lo == x.n_lo and (dx_in is None or (isinstance(dx_in, SplitRows) and dx_in.n_lo == x.n_lo))
-    xr, dor = x.c_rows(), dx_out.c_rows()
-    dir_ = dx_in.c_rows() if dx_in is not None else None
+    if split:
+        assert isinstance(dx_out, SplitRows) and dx_out.n_lo == x.n_lo and (dx_in is None or (isinstance(dx_in, SplitRows) and dx_in.n_lo == x.n_lo))
+        xr, dor = x.c_rows(), dx_out.c_rows()
+        dir_ = dx_in.c_rows() if dx_in is not None else None
+    else:
+        _chk2d(x, F32)
+        if dx_out is None:
+            dx_out = torch.empty((M, C), device=x.device, dtype=F32)
     nbytes = L.call("pvrl_layernorm_bwd_workspace_bytes", M, C)
     deferred = defer is not None
     ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8) if deferred else workspace(nbytes, x.device, "ln")
@@ -396,11 +363,16 @@ def _layernorm_bwd_split(dy, x, mean, rstd, gamma, dgamma, dbeta, dx_in, dx_out,
             if beta_acc != 0.0:
                 raise PvrlError("layernorm_bwd: dxsum_beta = 0 with beta_acc != 0 is not supported")
             tgt = torch.empty_like(dxsum)
-    L.call("pvrl_layernorm_bwd_split", _ptr(dy), _ld(dy), 1 if dy.dtype == F32 else 0, ctypes.addressof(xr), _ptr(mean), _ptr(rstd),
-           _ptr(gamma), ctypes.addressof(dir_) if dir_ is not None else None, ctypes.addressof(dor), float(beta_acc),
-           None if deferred else _ptr(dgamma), None if deferred else _ptr(dbeta), _ptr(ws), ws.numel(), M, C, _ptr(dxs),
-           _ld(dxs) if dxs is not None else 0, _ptr(dxs_scale), dxs.shape[0] if dxs is not None else 0, _ptr(tgt),
-           None if deferred else _ptr(gscale), None if deferred else _ptr(nonfinite), _stream())
+    head = (_ptr(dy), _ld(dy), 1 if dy.dtype == F32 else 0)
+    tail = (float(beta_acc), None if deferred else _ptr(dgamma), None if deferred else _ptr(dbeta), _ptr(ws), ws.numel(), M, C,
+            _ptr(dxs), _ld(dxs) if dxs is not None else 0, _ptr(dxs_scale), dxs.shape[0] if dxs is not None else 0, _ptr(tgt),
+            None if deferred else _ptr(gscale), None if deferred else _ptr(nonfinite), _stream())
+    if split:
+        L.call("pvrl_layernorm_bwd_split", *head, ctypes.addressof(xr), _ptr(mean), _ptr(rstd), _ptr(gamma),
+               ctypes.addressof(dir_) if dir_ is not None else None, ctypes.addressof(dor), *tail)
+    else:
+        L.call("pvrl_layernorm_bwd", *head, _ptr(x), _ld(x), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(dx_in),
+               _ld(dx_in) if dx_in is not None else 0, _ptr(dx_out), _ld(dx_out), *tail)
     if tgt is not dxsum:
         dxsum.mul_(float(dxsum_beta)).add_(tgt)
     if deferred:
@@ -446,9 +418,8 @@ def attn_t8_bwd(qkv, d_o, nseq, H, scale, dqkv=None):
     return dqkv
 
 
-def attn_fwd(qkv, nseq, S, H, scale, mode=0, T=1, cls_base=0, causal=False, kpm=None, o=None, o_cls=None, lse=None):
-    """o / o_cls must share a leading dimension (o_cls may be a row-slice of the same buffer)."""
-    L = lib()
+def _attn_fwd_outputs(qkv, nseq, S, H, mode, cls_base, o, o_cls, lse):
+    """checks and allocates what attn_fwd / attn_long_fwd write -> (o, o_cls, lse)"""
     _chk2d(qkv, OP16)
     if o is None:
         o = torch.empty((nseq * S if mode == 0 else cls_base, H * 64), device=qkv.device, dtype=OP16)
@@ -458,6 +429,29 @@ def attn_fwd(qkv, nseq, S, H, scale, mode=0, T=1, cls_base=0, causal=False, kpm=
         lse = torch.empty((nseq, H, S), device=qkv.device, dtype=F32)
     if o_cls is not None:
         assert _ld(o_cls) == _ld(o)
+    return o, o_cls, lse
+
+
+def _attn_bwd_outputs(qkv, nseq, mode, o, o_cls, d_o, d_o_cls, dqkv, dqkv_cls):
+    """checks and allocates what attn_bwd / attn_long_bwd write -> (dqkv, dqkv_cls)"""
+    _chk2d(qkv, OP16)
+    if dqkv is None:
+        dqkv = torch.empty_like(qkv)
+    if mode == 1 and dqkv_cls is None:
+        dqkv_cls = torch.empty((nseq, qkv.shape[1]), device=qkv.device, dtype=OP16)
+    if dqkv_cls is not None:
+        assert _ld(dqkv_cls) == _ld(dqkv)
+    if o_cls is not None:
+        assert _ld(o_cls) == _ld(o) == _ld(d_o) == _ld(d_o_cls)
+    else:
+        assert _ld(o) == _ld(d_o)
+    return dqkv, dqkv_cls
+
+
+def attn_fwd(qkv, nseq, S, H, scale, mode=0, T=1, cls_base=0, causal=False, kpm=None, o=None, o_cls=None, lse=None):
+    """o / o_cls must share a leading dimension (o_cls may be a row-slice of the same buffer)."""
+    L = lib()
+    o, o_cls, lse = _attn_fwd_outputs(qkv, nseq, S, H, mode, cls_base, o, o_cls, lse)
     L.call("pvrl_attn_fwd", _ptr(qkv), _ld(qkv), nseq, S, H, mode, T, cls_base, float(scale), 1 if causal else 0,
            _ptr(kpm), _ptr(o), _ptr(o_cls), _ld(o), _ptr(lse), _stream())
     return o, o_cls, lse
@@ -489,17 +483,7 @@ def attn_cls_bwd(qkv, o_cls, d_o_cls, lse, nseq, S, H, scale, T, cls_base, dqkv,
 def attn_bwd(qkv, o, o_cls, d_o, d_o_cls, lse, nseq, S, H, scale, mode=0, T=1, cls_base=0, causal=False, kpm=None,
              dqkv=None, dqkv_cls=None):
     L = lib()
-    _chk2d(qkv, OP16)
-    if dqkv is None:
-        dqkv = torch.empty_like(qkv)
-    if mode == 1 and dqkv_cls is None:
-        dqkv_cls = torch.empty((nseq, qkv.shape[1]), device=qkv.device, dtype=OP16)
-    if dqkv_cls is not None:
-        assert _ld(dqkv_cls) == _ld(dqkv)
-    if o_cls is not None:
-        assert _ld(o_cls) == _ld(o) == _ld(d_o) == _ld(d_o_cls)
-    else:
-        assert _ld(o) == _ld(d_o)
+    dqkv, dqkv_cls = _attn_bwd_outputs(qkv, nseq, mode, o, o_cls, d_o, d_o_cls, dqkv, dqkv_cls)
     dvec = torch.empty_like(lse)
     L.call("pvrl_attn_bwd", _ptr(qkv), _ld(qkv), nseq, S, H, mode, T, cls_base, float(scale), 1 if causal else 0,
            _ptr(kpm), _ptr(o), _ptr(o_cls), _ptr(d_o), _ptr(d_o_cls), _ld(o), _ptr(lse), _ptr(dvec), _ptr(dqkv),
@@ -521,15 +505,7 @@ def attn_uses_long(S):
 def attn_long_fwd(qkv, nseq, S, H, scale, mode=0, T=1, cls_base=0, o=None, o_cls=None, lse=None):
     """attn_fwd for 1 <= S <= ATTN_LONG_MAX_S without masks (pvrl_attn_long_fwd: streamed K / V, online softmax)"""
     L = lib()
-    _chk2d(qkv, OP16)
-    if o is None:
-        o = torch.empty((nseq * S if mode == 0 else cls_base, H * 64), device=qkv.device, dtype=OP16)
-    if mode == 1 and o_cls is None:
-        o_cls = torch.empty((nseq, H * 64), device=qkv.device, dtype=OP16)
-    if lse is None:
-        lse = torch.empty((nseq, H, S), device=qkv.device, dtype=F32)
-    if o_cls is not None:
-        assert _ld(o_cls) == _ld(o)
+    o, o_cls, lse = _attn_fwd_outputs(qkv, nseq, S, H, mode, cls_base, o, o_cls, lse)
     L.call("pvrl_attn_long_fwd", _ptr(qkv), _ld(qkv), nseq, S, H, mode, T, cls_base, float(scale), _ptr(o), _ptr(o_cls), _ld(o),
            _ptr(lse), _stream())
     return o, o_cls, lse
@@ -538,17 +514,7 @@ def attn_long_fwd(qkv, nseq, S, H, scale, mode=0, T=1, cls_base=0, o=None, o_cls
 def attn_long_bwd(qkv, o, o_cls, d_o, d_o_cls, lse, nseq, S, H, scale, mode=0, T=1, cls_base=0, dqkv=None, dqkv_cls=None):
     """backward of attn_long_fwd (pvrl_attn_long_bwd); deterministic, D = rowsum(dO * O) in the shared workspace"""
     L = lib()
-    _chk2d(qkv, OP16)
-    if dqkv is None:
-        dqkv = torch.empty_like(qkv)
-    if mode == 1 and dqkv_cls is None:
-        dqkv_cls = torch.empty((nseq, qkv.shape[1]), device=qkv.device, dtype=OP16)
-    if dqkv_cls is not None:
-        assert _ld(dqkv_cls) == _ld(dqkv)
-    if o_cls is not None:
-        assert _ld(o_cls) == _ld(o) == _ld(d_o) == _ld(d_o_cls)
-    else:
-        assert _ld(o) == _ld(d_o)
+    dqkv, dqkv_cls = _attn_bwd_outputs(qkv, nseq, mode, o, o_cls, d_o, d_o_cls, dqkv, dqkv_cls)
     nbytes = L.call("pvrl_attn_long_bwd_workspace_bytes", nseq, S, H)
     ws = workspace(nbytes, qkv.device, "attn_long")
     L.call("pvrl_attn_long_bwd", _ptr(qkv), _ld(qkv), nseq, S, H, mode, T, cls_base, float(scale), _ptr(o), _ptr(o_cls),
@@ -588,46 +554,37 @@ def _check_decoded(clips):
     return (fr.shape[0], None) if sh is None else (sh.shape[0], clips.src)
 
 
+def _decoded_launch(name, clips, B, src, *out_args):
+    """entry point `name` (its `_views` form for a transform.DecodedViews) on the decoded clips: the argument list up to the output"""
+    fr = clips.frames
+    S, T, H0, W0, _ = fr.shape
+    mean = (ctypes.c_float * 3)(*clips.mean)
+    std = (ctypes.c_float * 3)(*clips.std)
+    tail = (B, T, H0, W0, clips.crop, ctypes.cast(mean, ctypes.c_void_p), ctypes.cast(std, ctypes.c_void_p), *out_args, _stream())
+    if src is None:
+        lib().call(name, _ptr(fr), _ptr(clips.params), *tail)
+    else:
+        lib().call(name + "_views", _ptr(fr), _ptr(clips.params), _ptr(src), S, *tail)
+
+
 def frames_u8_patchify(clips, out=None):
     """transform.DecodedClips (uint8 [B,T,H0,W0,3] + per-clip draws) -> bf16 [(b,n,t), 768] of the normalised,
     rescaled, cropped, flipped clip (the reference's CPU-worker chain, fused into the im2col).  A transform.DecodedViews
     (B clips naming S shared source slabs) goes to the `_views` entry point: same arithmetic, same bits."""
-    import ctypes
-    L = lib()
-    fr = clips.frames
     B, src = _check_decoded(clips)
-    S, T, H0, W0, _ = fr.shape
-    crop = clips.crop
-    rows = B * (crop // 16) * (crop // 16) * T
     if out is None:
-        out = torch.empty((rows, 768), device=fr.device, dtype=OP16)
-    mean = (ctypes.c_float * 3)(*clips.mean)
-    std = (ctypes.c_float * 3)(*clips.std)
-    tail = (B, T, H0, W0, crop, ctypes.cast(mean, ctypes.c_void_p), ctypes.cast(std, ctypes.c_void_p), _ptr(out), _ld(out), _stream())
-    if src is None:
-        L.call("pvrl_frames_u8_patchify", _ptr(fr), _ptr(clips.params), *tail)
-    else:
-        L.call("pvrl_frames_u8_patchify_views", _ptr(fr), _ptr(clips.params), _ptr(src), S, *tail)
+        rows = B * (clips.crop // 16) * (clips.crop // 16) * clips.frames.shape[1]
+        out = torch.empty((rows, 768), device=clips.frames.device, dtype=OP16)
+    _decoded_launch("pvrl_frames_u8_patchify", clips, B, src, _ptr(out), _ld(out))
     return out
 
 
 def frames_u8_to_f32(clips):
     """transform.DecodedClips (or DecodedViews) -> fp32 [B, 3, T, crop, crop]: the tensor the reference's CPU workers would
     have produced"""
-    import ctypes
-    L = lib()
-    fr = clips.frames
     B, src = _check_decoded(clips)
-    S, T, H0, W0, _ = fr.shape
-    crop = clips.crop
-    out = torch.empty((B, 3, T, crop, crop), device=fr.device, dtype=F32)
-    mean = (ctypes.c_float * 3)(*clips.mean)
-    std = (ctypes.c_float * 3)(*clips.std)
-    tail = (B, T, H0, W0, crop, ctypes.cast(mean, ctypes.c_void_p), ctypes.cast(std, ctypes.c_void_p), _ptr(out), _stream())
-    if src is None:
-        L.call("pvrl_frames_u8_to_f32", _ptr(fr), _ptr(clips.params), *tail)
-    else:
-        L.call("pvrl_frames_u8_to_f32_views", _ptr(fr), _ptr(clips.params), _ptr(src), S, *tail)
+    out = torch.empty((B, 3, clips.frames.shape[1], clips.crop, clips.crop), device=clips.frames.device, dtype=F32)
+    _decoded_launch("pvrl_frames_u8_to_f32", clips, B, src, _ptr(out))
     return out
 
 

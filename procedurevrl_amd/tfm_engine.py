@@ -28,7 +28,7 @@ class StackEngine:
     the model's weights.WeightCache.get, or a caller's wrapper of it that adds a capture policy (head_engine)."""
 
     def __init__(self, resblocks, weight_cache, grad_target=None, heads=8, grad_store=None):
-        """`grad_store` (optional callable -> engine.GradStore): parameter gradients are then written in "fused" form -- the kernels
+        """`grad_store` (optional callable -> grads.GradStore): parameter gradients are then written in "fused" form -- the kernels
         take the fp16 flavour's backward scale out themselves and raise the optimiser's skip flag on a non-finite value
         (GradStore.target(..., fused=True)); without it `grad_target(p)` -> (tensor, beta) as before."""
         self.blocks = list(resblocks)

@@ -17,8 +17,9 @@ import torch.nn as nn
 
 from . import ops
 from .build import MODEL_REGISTRY
-from .engine import EncoderEngine, GradStore
+from .engine import EncoderEngine
 from .functional import EncoderFn, kl_topk_loss, l2norm, linear_f32, mse_loss, step_logits
+from .grads import GradStore
 from .head_engine import PretrainHeadEngine, PretrainHeadFn
 from .weights import WeightCache
 from .tfm_model import ClipTextModel, DiffusionTransformer as OrderTransformer

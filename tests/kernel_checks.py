@@ -140,7 +140,7 @@ def check_gemm_nt_batched():
 
 
 def check_grad_scale_begin():
-    """pvrl_grad_scale_begin (engine.GradStore.begin_scaled in one launch) vs the torch formula it replaces: S = the power of two that brings
+    """pvrl_grad_scale_begin (grads.GradStore.begin_scaled in one launch) vs the torch formula it replaces: S = the power of two that brings
     max|g| to the target, g * S exactly, 1 / S in every slot; zeros, inf and nan leave S a finite power of two."""
     from procedurevrl_amd import ops
     from procedurevrl_amd._lib import lib
@@ -509,6 +509,40 @@ def check_layernorm():
         out.append((f"ln_bwd unscaled column sums of the emitted rows (accumulating) {M}x{C}",
                     rel(cs, 2.0 + dx3.cpu()[:rows].sum(0)), 1e-5))
         out.append((f"ln_bwd dgamma with the column-sum output on {M}x{C}", rel(dg2, 1.0 + dg.cpu()), 1e-5))
+    return out
+
+
+def check_layernorm_bwd_refuses_before_launch():
+    """dxsum_beta = 0 with beta_acc = 1 and no `defer`: the kernel has one beta for its three sums, and the host side can only split
+    them for beta_acc = 0.  ops.layernorm_bwd raises PvrlError BEFORE anything is launched, for a plain x and for a SplitRows x:
+    every output, pre-filled with a sentinel, is bit-for-bit untouched (label value = elements changed, + 1 if nothing was raised)."""
+    from procedurevrl_amd import ops
+    from procedurevrl_amd._lib import PvrlError
+    g = torch.Generator().manual_seed(41)
+    M, C, rows16 = 4, 768, 3
+    x, dy = torch.randn(M, C, generator=g).to(dev()), torch.randn(M, C, generator=g).to(dev(), BF)
+    gam = torch.randn(C, generator=g).to(dev())
+    _, mean, rstd = ops.layernorm_fwd(x, gam, gam, 1e-6)
+    out = []
+    for kind in ("plain", "split"):
+        sent = lambda *shape, dtype=torch.float32: torch.full(shape, 3.25, device=dev(), dtype=dtype)
+        dg, db, dsum, dxs = sent(C), sent(C), sent(C), sent(M, C, dtype=BF)
+        if kind == "plain":
+            xin, dxo = x, sent(M, C)
+            outs = [dxo]
+        else:
+            xin = ops.SplitRows(x[:rows16].to(BF), x[rows16:].contiguous())
+            dxo = ops.SplitRows(sent(rows16, C, dtype=BF), sent(M - rows16, C))
+            outs = [dxo.lo, dxo.hi]
+        outs += [dg, db, dsum, dxs]
+        raised = 0
+        try:
+            ops.layernorm_bwd(dy, xin, mean, rstd, gam, dg, db, dx_out=dxo, beta_acc=1.0, dxs=dxs, dxsum=dsum, dxsum_beta=0.0)
+        except PvrlError:
+            raised = 1
+        torch.cuda.synchronize()
+        changed = sum(int((t != 3.25).sum()) for t in outs)
+        out.append((f"ln_bwd {kind}: dxsum_beta=0 with beta_acc=1 refused, outputs untouched", float(changed + 1 - raised), 0.0))
     return out
 
 
@@ -941,5 +975,5 @@ def check_input_pipeline():
     return out
 
 
-ALL_CHECKS = [check_input_pipeline, check_gemm_nt, check_gemm_nt_batched, check_small_batched, check_grad_scale_begin, check_gemm_f32_small, check_cls_linear, check_gemm_tn, check_gemm_tn_rows_behind_the_end, check_gemm_tn_repeatable, check_gemm_tn_into, check_gemm_tn_grouped, check_gemm_tn_grouped_block_size, check_cast_weights_multi, check_gemv_rows, check_layernorm, check_split_residual_stream, check_attn_t8, check_attn_cls,
+ALL_CHECKS = [check_input_pipeline, check_gemm_nt, check_gemm_nt_batched, check_small_batched, check_grad_scale_begin, check_gemm_f32_small, check_cls_linear, check_gemm_tn, check_gemm_tn_rows_behind_the_end, check_gemm_tn_repeatable, check_gemm_tn_into, check_gemm_tn_grouped, check_gemm_tn_grouped_block_size, check_cast_weights_multi, check_gemv_rows, check_layernorm, check_layernorm_bwd_refuses_before_launch, check_split_residual_stream, check_attn_t8, check_attn_cls,
               check_attn_mfma_contig, check_attn_mfma_spatial, check_attn_bwd_repeatable, check_elementwise, check_loss]
