@@ -36,6 +36,26 @@ __global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__
   }
 }
 
+// The arithmetic of the decoded-clip input pipeline, ONE copy for frames_u8_patchify_kernel and frames_u8_to_f32_kernel: a clip fed as
+// decoded uint8 and the same clip materialised as an fp32 tensor first must give the same bits.  Written inline in both kernels the
+// compiler contracted `scale * (d + 0.5f) - 0.5f` into an fma in one and left it a multiply and an add in the other (its choice
+// depends on the surrounding code), so their source coordinates -- and with them some 16-bit patch values -- differed by one rounding.
+// Contraction is off in here: every operation rounds once, as written (torch's area_pixel_compute_source_index / upsample_bilinear2d
+// order of operations).
+// source coordinate of output pixel `d`, align_corners=False, clamped at 0
+__device__ __forceinline__ float u8_src_coord(float scale, int d) {
+#pragma clang fp contract(off)
+  const float f = scale * ((float)d + 0.5f) - 0.5f;
+  return f < 0.f ? 0.f : f;
+}
+// bilinear sample of the four neighbours (row 0: a00 a01, row 1: a10 a11), then (v / 255 - mean) / std
+__device__ __forceinline__ float u8_pixel(float ly0, float ly1, float lx0, float lx1, float a00, float a01, float a10, float a11,
+                                          float mean, float istd) {
+#pragma clang fp contract(off)
+  const float v = ly0 * (lx0 * a00 + lx1 * a01) + ly1 * (lx0 * a10 + lx1 * a11);
+  return (v / 255.0f - mean) * istd;
+}
+
 // GPU-side input pipeline fused into the patch-embed im2col (reference: CPU workers run tensor_normalize ->
 // permute -> random_short_side_scale_jitter (bilinear, align_corners=False) -> crop -> horizontal flip,
 // lib/datasets/howto100m.py:437-452, lib/datasets/utils.py:110-160,309-326, lib/datasets/transform.py:8-147).
@@ -62,8 +82,7 @@ __global__ __launch_bounds__(256) void frames_u8_patchify_kernel(const unsigned 
     const int* q = prm + b * 5;
     const int nh = q[0], nw = q[1], yo = q[2], xo = q[3], flip = q[4];
     const float sy = (float)H0 / (float)nh, sx = (float)W0 / (float)nw;
-    float fy = sy * ((float)(y + yo) + 0.5f) - 0.5f;
-    fy = fy < 0.f ? 0.f : fy;
+    const float fy = u8_src_coord(sy, y + yo);
     const int y0 = (int)fy, y1 = y0 + (y0 < H0 - 1 ? 1 : 0);
     const float ly1 = fy - (float)y0, ly0 = 1.f - ly1;
     const int sb = VIEWS ? src[b] : b;
@@ -74,16 +93,13 @@ __global__ __launch_bounds__(256) void frames_u8_patchify_kernel(const unsigned 
     for (int e = 0; e < 8; ++e) {
       const int x = x8 * 8 + e;
       const int X = (flip ? crop - 1 - x : x) + xo;
-      float fx = sx * ((float)X + 0.5f) - 0.5f;
-      fx = fx < 0.f ? 0.f : fx;
+      const float fx = u8_src_coord(sx, X);
       const int x0 = (int)fx, x1 = x0 + (x0 < W0 - 1 ? 1 : 0);
       const float lx1 = fx - (float)x0, lx0 = 1.f - lx1;
 #pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const float v = ly0 * (lx0 * (float)f0[x0 * 3 + c] + lx1 * (float)f0[x1 * 3 + c]) +
-                        ly1 * (lx0 * (float)f1[x0 * 3 + c] + lx1 * (float)f1[x1 * 3 + c]);
-        o[c][e] = (op_t)((v / 255.0f - mean[c]) * istd[c]);
-      }
+      for (int c = 0; c < 3; ++c)
+        o[c][e] = (op_t)u8_pixel(ly0, ly1, lx0, lx1, (float)f0[x0 * 3 + c], (float)f0[x1 * 3 + c], (float)f1[x0 * 3 + c],
+                                 (float)f1[x1 * 3 + c], mean[c], istd[c]);
     }
     const int n = (y >> 4) * PW + (x8 >> 1);
     const long row = ((long)b * (crop >> 4) * PW + n) * T + t;
@@ -115,8 +131,7 @@ __global__ __launch_bounds__(256) void frames_u8_to_f32_kernel(const unsigned ch
     const int* q = prm + b * 5;
     const int nh = q[0], nw = q[1], yo = q[2], xo = q[3], flip = q[4];
     const float sy = (float)H0 / (float)nh, sx = (float)W0 / (float)nw;
-    float fy = sy * ((float)(y + yo) + 0.5f) - 0.5f;
-    fy = fy < 0.f ? 0.f : fy;
+    const float fy = u8_src_coord(sy, y + yo);
     const int y0 = (int)fy, y1 = y0 + (y0 < H0 - 1 ? 1 : 0);
     const float ly1 = fy - (float)y0, ly0 = 1.f - ly1;
     const int sb = VIEWS ? src[b] : b;
@@ -127,12 +142,10 @@ __global__ __launch_bounds__(256) void frames_u8_to_f32_kernel(const unsigned ch
     for (int e = 0; e < 4; ++e) {
       const int x = x4 * 4 + e;
       const int X = (flip ? crop - 1 - x : x) + xo;
-      float fx = sx * ((float)X + 0.5f) - 0.5f;
-      fx = fx < 0.f ? 0.f : fx;
+      const float fx = u8_src_coord(sx, X);
       const int x0 = (int)fx, x1 = x0 + (x0 < W0 - 1 ? 1 : 0);
       const float lx1 = fx - (float)x0, lx0 = 1.f - lx1;
-      const float v = ly0 * (lx0 * (float)f0[x0 * 3] + lx1 * (float)f0[x1 * 3]) + ly1 * (lx0 * (float)f1[x0 * 3] + lx1 * (float)f1[x1 * 3]);
-      o[e] = (v / 255.0f - mean[c]) * istd[c];
+      o[e] = u8_pixel(ly0, ly1, lx0, lx1, (float)f0[x0 * 3], (float)f0[x1 * 3], (float)f1[x0 * 3], (float)f1[x1 * 3], mean[c], istd[c]);
     }
     *reinterpret_cast<f32x4*>(out + idx * 4) = o;
   }

@@ -116,6 +116,13 @@ class EncoderEngine(GraphReplay):
         self._graph_init()            # HIP-graph replay of the step (GraphReplay)
         self._refreshed = False
         assert self.C == 768 and self.C // self.H == 64, "kernels are built for ViT-B (C=768, head_dim=64)"
+        # the geometry the model was built for (DATA.TRAIN_CROP_SIZE, DATA.NUM_FRAMES) against the attention kernels' limits: a clear
+        # error here instead of PVRL_EINVAL from inside the first block (a forward checks its input's own geometry again)
+        self._check_geometry(model.patch_embed.num_patches, model.time_embed.shape[1] if hasattr(model, "time_embed") else 1)
+
+    def _check_geometry(self, N, T, **keys):
+        scheme = getattr(self.m, "attention_type", "divided_space_time")
+        ops.check_attn_geometry(N, T, scheme, self.prune_last and self.prune_attn, **keys)
 
     # ------------------------------------------------------------------ weights
     def _weight(self, p, need_t=True):
@@ -361,6 +368,9 @@ class EncoderEngine(GraphReplay):
         return self._forward(frames, training, droppath, save)
 
     def _forward(self, frames, training, droppath=None, save=True):
+        # the input's own geometry (a test crop may differ from the model's) against the kernels' limits, before the first launch
+        self._check_geometry((frames.shape[3] // 16) * (frames.shape[4] // 16), frames.shape[2],
+                             crop_key="input crop (DATA.TRAIN_CROP_SIZE / DATA.TEST_CROP_SIZE)", frames_key="input frames (DATA.NUM_FRAMES)")
         L = lib()
         m = self.m
         self._refresh_weights()
@@ -531,7 +541,8 @@ class EncoderEngine(GraphReplay):
             _, lse_s = ops.attn_cls_fwd(qkv_s, B * T, N + 1, H, self.scale, T, R, o_cls=o_s[R:])
         else:
             qkv_s = ops.gemm_nt(h_s, wqkv, L.PVRL_EPI_BF16, bias=P(blk.attn.qkv.bias))
-            _, _, lse_s = ops.attn_fwd(qkv_s, B * T, N + 1, H, self.scale, mode=1, T=T, cls_base=R, o=o_s[:R], o_cls=o_s[R:])
+            # (N + 1 tokens per frame: the whole-sequence kernels up to ops.ATTN_MAX_S, the streamed ones for crops above 320^2)
+            _, _, lse_s = ops.attn_seq_fwd(qkv_s, B * T, N + 1, H, self.scale, mode=1, T=T, cls_base=R, o=o_s[:R], o_cls=o_s[R:])
         x2 = _X.new(R, B, C, dev, split)      # (pruned last block: its patch rows are neither computed nor defined)
         if prune:
             self._undef(x2.p)
@@ -575,9 +586,8 @@ class EncoderEngine(GraphReplay):
     def _attn_undivided(self, qkv, B, S, R, o):
         """one sequence per sample: its cls row R + b, then its S - 1 patch rows -- the kernels' mode 1 with T = 1, whose token-0 side
         buffers are then the cls rows of the same matrices.  Up to ops.ATTN_MAX_S tokens the whole-sequence kernels, beyond them the
-        streamed ones (ops.attn_uses_long)."""
-        fwd = ops.attn_long_fwd if ops.attn_uses_long(S) else ops.attn_fwd
-        return fwd(qkv, B, S, self.H, self.scale, mode=1, T=1, cls_base=R, o=o[:R], o_cls=o[R:])[2]
+        streamed ones (ops.attn_family, the one dispatch rule of every scheme)."""
+        return ops.attn_seq_fwd(qkv, B, S, self.H, self.scale, mode=1, T=1, cls_base=R, o=o[:R], o_cls=o[R:])[2]
 
     def _block_fwd_undivided(self, blk, x0, sv, dp, save):
         """x += dp * proj(attn(norm1(x))); x += dp * mlp(norm2(x))   (Block.forward, vit.py:124-127) on the rows of `_X`.  No pruning of
@@ -636,9 +646,8 @@ class EncoderEngine(GraphReplay):
         del dps
         S = N * T + 1
         dqkv = torch.empty((M, 3 * C), device=dev, dtype=OP16)
-        bwd = ops.attn_long_bwd if ops.attn_uses_long(S) else ops.attn_bwd
-        bwd(s["qkv_s"], s["o_s"][:R], s["o_s"][R:], do[:R], do[R:], s["lse_s"], B, S, H, self.scale, mode=1, T=1, cls_base=R,
-            dqkv=dqkv, dqkv_cls=dqkv[R:])
+        ops.attn_seq_bwd(s["qkv_s"], s["o_s"][:R], s["o_s"][R:], do[:R], do[R:], s["lse_s"], B, S, H, self.scale, mode=1, T=1, cls_base=R,
+                         dqkv=dqkv, dqkv_cls=dqkv[R:])
         self._lin_wgrad(gs, dqkv, s["h_s"], blk.attn.qkv)
         dh = ops.gemm_nt(dqkv, self._weight(blk.attn.qkv.weight).t, L.PVRL_EPI_BF16)
         del dqkv, do
@@ -844,8 +853,8 @@ class EncoderEngine(GraphReplay):
             ops.gemm_nt(dqkv[R:M], wt, L.PVRL_EPI_BF16, out0=dh[R:])
             del wq
         else:
-            ops.attn_bwd(s["qkv_s"], s["o_s"][:R], s["o_s"][R:], do[:R], do[R:], s["lse_s"], B * T, N + 1, H, self.scale,
-                         mode=1, T=T, cls_base=R, dqkv=dqkv[:M], dqkv_cls=dqkv[M:])
+            ops.attn_seq_bwd(s["qkv_s"], s["o_s"][:R], s["o_s"][R:], do[:R], do[R:], s["lse_s"], B * T, N + 1, H, self.scale,
+                             mode=1, T=T, cls_base=R, dqkv=dqkv[:M], dqkv_cls=dqkv[M:])
             ops.group_reduce(dqkv[M:], B, T, out=dqkv[R:M])
             self._lin_wgrad(gs, dqkv[:M], s["h_s"], blk.attn.qkv)
             dh = ops.gemm_nt(dqkv[:M], self._weight(blk.attn.qkv.weight).t, L.PVRL_EPI_BF16)

@@ -497,9 +497,57 @@ ATTN_LONG_KT, ATTN_LONG_QT, ATTN_LONG_MAX_S = _HC["PVRL_ATTN_LONG_KT"], _HC["PVR
 ATTN_MAX_S = 416      # the longest sequence pvrl_attn_fwd / _bwd keep in LDS (csrc/attn_common.h, ATT_ROWS_LONG)
 
 
+ATTN_CLS_MAX_S = 4096  # the longest sequence pvrl_attn_cls_fwd / _bwd take (csrc/attn_cls.hip)
+
+
+def attn_family(S):
+    """THE attention dispatch rule, a pure function of the sequence length -- every scheme's unmasked attention goes through it (the
+    divided scheme's spatial branch and the undivided schemes alike: attn_seq_fwd / attn_seq_bwd below):
+        "whole"     S <= ATTN_MAX_S           attn_fwd / attn_bwd: a whole sequence in LDS
+        "streamed"  S <= ATTN_LONG_MAX_S      attn_long_fwd / attn_long_bwd: K / V streamed through LDS, online softmax
+    Beyond ATTN_LONG_MAX_S no kernel exists: NotImplementedError."""
+    if S <= ATTN_MAX_S:
+        return "whole"
+    if S <= ATTN_LONG_MAX_S:
+        return "streamed"
+    raise NotImplementedError(f"attention over {S} tokens: the streamed kernels take at most ATTN_LONG_MAX_S = {ATTN_LONG_MAX_S}")
+
+
 def attn_uses_long(S):
-    """the undivided schemes' attention dispatch: sequences of more than ATTN_MAX_S tokens take attn_long_fwd / _bwd"""
-    return S > ATTN_MAX_S
+    """attn_family(S) as a flag: sequences of more than ATTN_MAX_S tokens take attn_long_fwd / _bwd, whatever the attention scheme"""
+    return attn_family(S) == "streamed"
+
+
+def attn_seq_fwd(qkv, nseq, S, H, scale, **kw):
+    """attn_fwd or attn_long_fwd (same arguments, same results) as attn_family(S) says; no masks"""
+    return (attn_long_fwd if attn_uses_long(S) else attn_fwd)(qkv, nseq, S, H, scale, **kw)
+
+
+def attn_seq_bwd(qkv, o, o_cls, d_o, d_o_cls, lse, nseq, S, H, scale, **kw):
+    """attn_bwd or attn_long_bwd as attn_family(S) says"""
+    return (attn_long_bwd if attn_uses_long(S) else attn_bwd)(qkv, o, o_cls, d_o, d_o_cls, lse, nseq, S, H, scale, **kw)
+
+
+def check_attn_geometry(N, T, scheme, prune_attn, crop_key="DATA.TRAIN_CROP_SIZE", frames_key="DATA.NUM_FRAMES"):
+    """The attention kernels' limits for N patches per frame and T frames under TIMESFORMER.ATTENTION_TYPE `scheme`, checked on the host
+    before anything is launched: NotImplementedError naming the limit and the key that sets the offending size (`crop_key` /
+    `frames_key`: the config keys at construction, the input's own sizes in a forward)."""
+    if scheme == "divided_space_time":
+        if N + 1 > ATTN_LONG_MAX_S:
+            raise NotImplementedError(f"{crop_key}: {N} patches + cls = {N + 1} tokens per frame exceed ATTN_LONG_MAX_S = "
+                                      f"{ATTN_LONG_MAX_S}, the streamed spatial attention's limit")
+        if prune_attn and N + 1 > ATTN_CLS_MAX_S:
+            raise NotImplementedError(f"{crop_key}: {N} patches + cls = {N + 1} tokens per frame exceed ATTN_CLS_MAX_S = "
+                                      f"{ATTN_CLS_MAX_S}, the limit of the last block's cls-query attention (PVRL_PRUNE_ATTN=0 runs "
+                                      f"that block on the streamed kernels)")
+        if T > ATTN_MAX_S:
+            raise NotImplementedError(f"{frames_key}: {T} frames exceed ATTN_MAX_S = {ATTN_MAX_S}, the temporal attention's limit")
+    else:
+        S = (N if scheme == "space_only" else N * T) + 1
+        if S > ATTN_LONG_MAX_S:
+            keys = crop_key if scheme == "space_only" else f"{crop_key} x {frames_key}"
+            raise NotImplementedError(f"{keys}: {S} tokens per {scheme} sequence exceed ATTN_LONG_MAX_S = {ATTN_LONG_MAX_S}, the "
+                                      f"streamed attention's limit")
 
 
 def attn_long_fwd(qkv, nseq, S, H, scale, mode=0, T=1, cls_base=0, o=None, o_cls=None, lse=None):

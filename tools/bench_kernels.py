@@ -190,26 +190,34 @@ def main():
 
     if want("attn_long"):
         # The streamed long-sequence attention (csrc/attn_long.hip) at joint space-time attention's shapes -- 32 clips x 12 heads x 1,569
-        # tokens (8 x 224^2) and 4 x 12 x 6,273 (32 x 224^2) -- in alternating rounds with torch's scaled_dot_product_attention on the
-        # same values in the same process; the median round counts.  FLOPs: 4 S^2 64 per (clip, head) forward; the backward's EXECUTED
-        # products: seven here (S and dP are formed in both backward kernels), five assumed for the baseline.
+        # tokens (8 x 224^2) and 4 x 12 x 6,273 (32 x 224^2) -- and at the divided scheme's TimeSformer-HR shape: 32 clips x 16 frames =
+        # 512 sequences of 785 tokens (448^2), the 16 sequences of a clip sharing its cls row (mode 1, T = 16) -- in alternating rounds
+        # with torch's scaled_dot_product_attention on the same values in the same process; the median round counts.  FLOPs: 4 S^2 64
+        # per (sequence, head) forward; the backward's EXECUTED products: seven here (S and dP are formed in both backward kernels),
+        # five assumed for the baseline.
         import statistics
         import torch.nn.functional as F
         OP = ops.OP16
-        for Bl, Hl, Sl in ((32, 12, 1569), (4, 12, 6273)):
-            Rl = Bl * (Sl - 1)
+        for Bl, Tl, Hl, Sl in ((32, 1, 12, 1569), (4, 1, 12, 6273), (32, 16, 12, 785)):
+            nl, Nl = Bl * Tl, Sl - 1
+            Rl = Bl * Nl * Tl
             qkv = rnd(Rl + Bl, 3 * Hl * 64).to(OP)
-            do = rnd(Rl + Bl, Hl * 64).to(OP)
-            o = torch.empty(Rl + Bl, Hl * 64, device=DEV, dtype=OP)
-            dq = torch.empty(Rl + Bl, 3 * Hl * 64, device=DEV, dtype=OP)
-            kw = dict(mode=1, T=1, cls_base=Rl)
-            ff = lambda: ops.attn_long_fwd(qkv, Bl, Sl, Hl, 0.125, o=o[:Rl], o_cls=o[Rl:], **kw)
+            do = rnd(Rl + nl, Hl * 64).to(OP)
+            o = torch.empty(Rl + nl, Hl * 64, device=DEV, dtype=OP)
+            dq = torch.empty(Rl + Bl + nl, 3 * Hl * 64, device=DEV, dtype=OP)      # (T = 1: the cls partial rows ARE the cls rows)
+            dq_cls = dq[Rl:Rl + Bl] if Tl == 1 else dq[Rl + Bl:]
+            kw = dict(mode=1, T=Tl, cls_base=Rl)
+            ff = lambda: ops.attn_long_fwd(qkv, nl, Sl, Hl, 0.125, o=o[:Rl], o_cls=o[Rl:], **kw)
             lse = ff()[2]
-            fb = lambda: ops.attn_long_bwd(qkv, o[:Rl], o[Rl:], do[:Rl], do[Rl:], lse, Bl, Sl, Hl, 0.125, dqkv=dq, dqkv_cls=dq[Rl:], **kw)
-            # the same sequences as [B, H, S, 64] tensors: cls row first, then the clip's patch rows
-            seq = torch.cat([qkv[Rl:].view(Bl, 1, -1), qkv[:Rl].view(Bl, Sl - 1, -1)], 1).view(Bl, Sl, 3, Hl, 64).permute(2, 0, 3, 1, 4)
+            fb = lambda: ops.attn_long_bwd(qkv, o[:Rl], o[Rl:], do[:Rl], do[Rl:], lse, nl, Sl, Hl, 0.125, dqkv=dq[:Rl + Bl], dqkv_cls=dq_cls, **kw)
+            # the same sequences as [nseq, H, S, 64] tensors: the clip's cls row first, then the patch rows (b, n, t) of frame t
+            def seqs(x, cls):
+                W = x.shape[1]
+                pat = x[:Rl].view(Bl, Nl, Tl, W).permute(0, 2, 1, 3)
+                return torch.cat([cls.view(Bl, Tl, 1, W), pat], 2).reshape(nl, Sl, W)
+            seq = seqs(qkv, qkv[Rl:].view(Bl, 1, -1).expand(Bl, Tl, -1)).view(nl, Sl, 3, Hl, 64).permute(2, 0, 3, 1, 4)
             q, k, v = (t.contiguous().requires_grad_(True) for t in seq)
-            dos = torch.cat([do[Rl:].view(Bl, 1, -1), do[:Rl].view(Bl, Sl - 1, -1)], 1).view(Bl, Sl, Hl, 64).permute(0, 2, 1, 3).contiguous()
+            dos = seqs(do, do[Rl:]).view(nl, Sl, Hl, 64).permute(0, 2, 1, 3).contiguous()
             sf = lambda: F.scaled_dot_product_attention(q, k, v, scale=0.125)
             os_ = sf()
             sb = lambda: torch.autograd.grad(os_, (q, k, v), dos, retain_graph=True)
@@ -218,8 +226,8 @@ def main():
                 for n, fn in (("ff", ff), ("sf", sf), ("fb", fb), ("sb", sb)):
                     t[n].append(timeit(fn, reps=5, warm=1))
             med = {n: statistics.median(v) for n, v in t.items()}
-            fl = 4.0 * Bl * Hl * Sl * Sl * 64
-            tag = f"{Bl}x{Hl}xS{Sl}"
+            fl = 4.0 * nl * Hl * Sl * Sl * 64
+            tag = f"{Bl}x{Hl}xS{Sl}" if Tl == 1 else f"{Bl}x{Tl}x{Hl}xS{Sl} T={Tl}"
             rows.append((f"attn_long fwd {tag}", med["ff"], fl / med["ff"] / 1e6))
             rows.append((f"torch sdpa fwd {tag}", med["sf"], fl / med["sf"] / 1e6))
             rows.append((f"attn_long bwd {tag} (7 products)", med["fb"], 3.5 * fl / med["fb"] / 1e6))
