@@ -133,10 +133,12 @@ int64_t pvrl_gemm_tn_grouped_workspace_bytes(int nprob, const pvrl_tn_problem* p
 int pvrl_gemm_tn_grouped_bf16(int nprob, const pvrl_tn_problem* problems, int64_t splits, void* workspace,
                               int64_t workspace_bytes, void* stream);
 
-/* LayerNorm over fp32 rows, C in {512, 768} (vit.py:104,109,116,228 eps 1e-6; tfm_model.py:18-24 eps 1e-5).
+/* LayerNorm over fp32 rows, C in {512, 768, 1024} (vit.py:104,109,116,228 eps 1e-6 at ViT-B's and ViT-L's width; tfm_model.py:18-24
+ * eps 1e-5); any other C is PVRL_EINVAL (a lane holds C / 256 float4s of a row: C = 384 would need another row mapping).
  * fwd: y = (x - mean) * rstd * gamma + beta  -> bf16 (GEMM operand) or fp32.
  * bwd: dx_out = dx_in(optional) + dLN; dgamma/dbeta = beta_acc * old + sums over rows; optionally also writes
- *      dxs_bf16[m] = bf16(dxs_scale[m] * dx_out[m]) for m < dxs_rows (the next stage's bf16 GEMM operand, DropPath-scaled)
+ *      dxs_bf16[m] = bf16(dxs_scale[m] * dx_out[m]) for m < dxs_rows (the next stage's bf16 GEMM operand, DropPath-scaled;
+ *      dxs_scale has dxs_rows entries and nothing behind them is read)
  *      and dxsum[c] = beta_acc * old + sum over m < dxs_rows of dx_out[m][c] (the UNscaled column sums = the gradient of a
  *      bias added after the DropPath scale, optional).  gscale / nonfinite: see pvrl_gemm_tn_bf16 (dgamma, dbeta and dxsum are
  *      parameter gradients: beta_acc * old + gscale * sums). */

@@ -142,13 +142,13 @@ template <int NW>
 int launch_cls(const ClsLin& p, int epi, hipStream_t s) {
   const int kw = p.K / p.ksplit / NW;
   if (kw % 96 == 0) return launch_cls_ku<NW, 6>(p, epi, s);      // ViT-B: 768 / 8, and 3072 in four slices
-  if (kw % 32 == 0) return launch_cls_ku<NW, 2>(p, epi, s);
+  if (kw % 32 == 0) return launch_cls_ku<NW, 2>(p, epi, s);      // ViT-L: 1024 / 8 = 128, and 4096 in four slices (no KU of its own: none was measured)
   return launch_cls_ku<NW, 1>(p, epi, s);
 }
 
 }  // namespace
 
-// slices of K: the long reductions with few column tiles (fc2: N = 768, K = 3072 -> 4 x 48 workgroups)
+// slices of K: the long reductions with few column tiles (fc2: N = 768, K = 3072 -> 4 x 48 workgroups; N = 1024, K = 4096 -> 4 x 64)
 static int cls_ksplit(int64_t N, int64_t K) { return (K >= 2048 && K % 1024 == 0 && N / 16 < 128) ? 4 : 1; }
 
 extern "C" int64_t pvrl_cls_linear_f32_workspace_bytes(int64_t M, int64_t N, int64_t K) {

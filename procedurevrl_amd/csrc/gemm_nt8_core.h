@@ -346,7 +346,11 @@ int launch_nt8(GemmNT p, hipStream_t s) {
   p.tiles_m = cdiv(p.M, 256);
   if (p.gm <= 0) p.gm = NT_GM;
   const int qm = p.tiles_m >> 3, rm = p.tiles_m & 7;
-  const int nb = nt8_plan(qm + (rm ? 1 : 0), p.tiles_n, p.cus, p.tails).nblk;      // the longest per-XCD list
+  // XCDs own ceil or floor(tiles_m / 8) panels; the longer per-XCD list sizes the grid.  That can be the FLOOR list: below one round
+  // its tiles may go out as 2 L half items where the ceil list stays whole (19 panels x 8 column tiles: 24 tiles next to 2 x 16 halves),
+  // and a workgroup takes at most ONE half item, as its last -- a grid sized by the ceil list alone left the halves behind it unwritten
+  int nb = nt8_plan(qm + (rm ? 1 : 0), p.tiles_n, p.cus, p.tails).nblk;
+  if (qm > 0) nb = std::max(nb, nt8_plan(qm, p.tiles_n, p.cus, p.tails).nblk);
   p.nwg = 8 * std::min(nb, p.cus);                                                  // one persistent workgroup per CU
   hipLaunchKernelGGL((gemm_nt8_kernel<EPI>), dim3(p.nwg), dim3(512), 0, s, p);
   PVRL_LAUNCH_CHECK();

@@ -162,8 +162,9 @@ __device__ __forceinline__ void ln_bwd_rows(int row0, int row1, int bid, int nb,
       rowv[r] = row;
       mu[r] = mean[row];
       rs[r] = rstd[row];
-      // the DropPath factor of the emitted copy: an UNCONDITIONAL load (of a harmless address when there is no factor) with the others
-      sc[r] = *(dxs_scale ? dxs_scale + row : mean + row);
+      // the DropPath factor of the emitted copy: an UNCONDITIONAL load (of a harmless address when there is no factor, or no entry
+      // for this row: the vector has dxs_rows entries, and the cls rows behind them may lie past its allocation) with the others
+      sc[r] = *(dxs_scale && row < dxs_rows ? dxs_scale + row : mean + row);
       // the incoming residual gradient is not needed before the row reductions, but its load goes out WITH x and dy: one
       // memory round trip per row instead of two
       const TX* dir = Part<LO>::row(dx_in, row);
@@ -283,7 +284,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const TDy* __restrict__ dy,
 // out[j] = beta*out[j] + gscale * sum_b part[b][j]   (j over 2*C: dgamma then dbeta); gscale / nonfinite as in gemm_tn_core.h: the
 // scale of the fp16 flavour's S-scaled backward is taken out where the parameter gradient is written, and a non-finite value
 // written raises the optimiser's skip flag
-// 16 columns x 16 row groups per block (64-byte row segments), LDS tree at the end: 96 blocks for C = 768.
+// 16 columns x 16 row groups per block (64-byte row segments), LDS tree at the end: 2 C / 16 blocks (96 for C = 768,
+// 128 for C = 1024); a workgroup's partials are (2 + want_sum) C floats, whatever C.
 __global__ __launch_bounds__(256) void colpart_reduce_kernel(const float* __restrict__ part, int nblk, int n, float beta,
                                                              float* __restrict__ out0, float* __restrict__ out1,
                                                              int half, int pstride, const float* __restrict__ gscale,
@@ -370,7 +372,7 @@ extern "C" int pvrl_layernorm_fwd_split(const void* x16, int64_t ldx16, int64_t 
   else                                                                                                              \
     hipLaunchKernelGGL((ln_fwd_kernel<CC, op_t>), grid, blk, 0, s, xr, gamma, beta, eps, (op_t*)y,                   \
                        (long)ldy, mean, rstd, (int)M, nb_lo);
-  if (C == 768) { LN_FWD(768) } else if (C == 512) { LN_FWD(512) } else return PVRL_EINVAL;
+  if (C == 768) { LN_FWD(768) } else if (C == 1024) { LN_FWD(1024) } else if (C == 512) { LN_FWD(512) } else return PVRL_EINVAL;
 #undef LN_FWD
   PVRL_LAUNCH_CHECK();
   return PVRL_OK;
@@ -422,7 +424,7 @@ extern "C" int pvrl_layernorm_bwd_split(const void* dy, int64_t lddy, int dy_is_
     hipLaunchKernelGGL((ln_bwd_kernel<CC, op_t>), dim3(nblk), dim3(256), 0, s, (const op_t*)dy, (long)lddy, xr,       \
                        mean, rstd, gamma, dxi, dxo, part, (int)M,                                                    \
                        (op_t*)dxs_bf16, (long)ldxs, dxs_scale, (int)dxs_rows, want_sum, nb_hi);
-  if (C == 768) { LN_BWD(768) } else if (C == 512) { LN_BWD(512) } else return PVRL_EINVAL;
+  if (C == 768) { LN_BWD(768) } else if (C == 1024) { LN_BWD(1024) } else if (C == 512) { LN_BWD(512) } else return PVRL_EINVAL;
 #undef LN_BWD
   PVRL_LAUNCH_CHECK();
   if (!dgamma) return PVRL_OK;       // deferred: the partials stay in `workspace` for pvrl_layernorm_bwd_reduce_batched
@@ -461,7 +463,7 @@ extern "C" int pvrl_layernorm_bwd_reduce_batched(int n, const pvrl_ln_reduce* it
     int blocks = 0;
     for (int i = 0; i < g.n; ++i) {
       const pvrl_ln_reduce& q = items[i0 + i];
-      if (!q.part || !q.dgamma || !q.dbeta || q.M <= 0 || (q.C != 768 && q.C != 512) || (q.want_sum && !q.dxsum)) return PVRL_EINVAL;
+      if (!q.part || !q.dgamma || !q.dbeta || q.M <= 0 || (q.C != 768 && q.C != 1024 && q.C != 512) || (q.want_sum && !q.dxsum)) return PVRL_EINVAL;
       LnReduceItem& w = g.it[i];
       w.part = q.part; w.C = (int)q.C;
       w.nblk = ln_bwd_nblk(q.M);

@@ -4,7 +4,7 @@ This is the host side of the hot path `VisionTransformer.forward_features`
 (reference lib/models/vit.py:365-423) and its autograd backward, restated as an explicit
 schedule of C-ABI kernel launches (include/pvrl.h) on torch's current HIP stream.
 
-Token layout (the residual stream x has M = B*N*T + B rows of 768 channels):
+Token layout (the residual stream x has M = B*N*T + B rows of C = embed_dim channels: 768 for ViT-B, 1024 for ViT-L):
     rows [0, R)   patch tokens ordered (b, n, t), t innermost      R = B*N*T     16-bit operand type since round 6 (`_X`, resid16)
     rows [R, M)   the cls token of clip b                                        fp32
 The reference keeps [B, 1 + N*T, C] and re-gathers it with einops for every branch
@@ -84,7 +84,7 @@ class EncoderEngine(GraphReplay):
         # its graph truly co-run), the capture segfaults inside ROCm 7 at 1-2 queues, and under a foreign stream's long kernel (RCCL)
         # it stalls behind whatever shares its queue (tools/probe/comm_cus_ab.py).  Grouped weight-gradient launches fill the chip on
         # their own; there is nothing to overlap.
-        # the 768^3 GEMMs of the fused temporal branch (W_e per block in forward; dW_fc, dW_proj per block in backward) are batched into
+        # the C^3 GEMMs of the fused temporal branch (W_e per block in forward; dW_fc, dW_proj per block in backward) are batched into
         # one launch per dozen (ops.gemm_nt_batched): 36 tiles apiece cannot fill 256 CUs
         # with a gradient hook (data parallel): blocks per group -- the hook runs (and the deferred launches go out, batched) once per
         # group of this many blocks instead of per block: four all-reduce rounds of ~135 MB per backward instead of twelve of 45
@@ -115,7 +115,8 @@ class EncoderEngine(GraphReplay):
         self._keep = None
         self._graph_init()            # HIP-graph replay of the step (GraphReplay)
         self._refreshed = False
-        assert self.C == 768 and self.C // self.H == 64, "kernels are built for ViT-B (C=768, head_dim=64)"
+        # the sizes the kernels serve, ViT-B (768, 12) and ViT-L (1024, 16): a clear error here for any other pair
+        ops.check_encoder_width(self.C, self.H)
         # the geometry the model was built for (DATA.TRAIN_CROP_SIZE, DATA.NUM_FRAMES) against the attention kernels' limits: a clear
         # error here instead of PVRL_EINVAL from inside the first block (a forward checks its input's own geometry again)
         self._check_geometry(model.patch_embed.num_patches, model.time_embed.shape[1] if hasattr(model, "time_embed") else 1)
@@ -145,7 +146,7 @@ class EncoderEngine(GraphReplay):
         """The temporal branch applies two linear maps back to back (vit.py:131-134: temporal_attn.proj, DropPath, then
         temporal_fc), so  x + fc(rs * proj(o)) = x + rs * (o W_e^T + b_e) + b_fc  with  W_e = W_fc W_proj,  b_e = W_fc b_proj:
         ONE 50k-row GEMM forward (and one data-gradient / one weight-gradient GEMM backward) instead of two each.
-        W_e is rebuilt from the bf16 operand copies whenever either weight changed (a 768^3 MFMA GEMM); the parameter
+        W_e is rebuilt from the bf16 operand copies whenever either weight changed (a C^3 MFMA GEMM); the parameter
         gradients are recovered from dW_e in backward (`_temporal_chain_all`)."""
         wf, wp = blk.temporal_fc.weight, blk.temporal_attn.proj.weight
         e = self.weights.entry(wf, "fused_t")
@@ -172,8 +173,8 @@ class EncoderEngine(GraphReplay):
         return ef is None or ep is None or e.ver != (ef.ver, ep.ver, blk.temporal_attn.proj.bias._version)
 
     def _build_fused_all(self):
-        """W_e = W_fc W_proj (and b_e) of every block whose weights changed, at the start of a forward: ONE batched launch of the twelve
-        768^3 GEMMs and one of the twelve casts instead of a 16.6-us GEMM + a cast in front of every block's temporal GEMM."""
+        """W_e = W_fc W_proj (and b_e) of every block whose weights changed, at the start of a forward: ONE batched launch of the blocks'
+        C^3 GEMMs and one of their casts instead of a GEMM (16.6 us at C = 768) + a cast in front of every block's temporal GEMM."""
         self._fused_fresh = set()
         if self.undivided:
             return
@@ -210,7 +211,7 @@ class EncoderEngine(GraphReplay):
         """dW_e [out, in], db_e [out] (fp32, from the weight-gradient GEMM of each fused map the backward queued) -> gradients of the
         four parameters:  dW_fc = dW_e W_proj^T + db_e b_proj^T,  dW_proj = W_fc^T dW_e,  db_proj = W_fc^T db_e  (db_fc comes from the
         LayerNorm backward's column sums).  Nobody needs a block's gradients before the end of the backward (of its group, under a
-        gradient hook): the 2 x 12 GEMMs as batched launches, the twelve casts as one."""
+        gradient hook): the two GEMMs per block as batched launches, the blocks' casts as one."""
         chain, self._chain = self._chain, []
         if not chain:
             return

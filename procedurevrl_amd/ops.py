@@ -528,6 +528,21 @@ def attn_seq_bwd(qkv, o, o_cls, d_o, d_o_cls, lse, nseq, S, H, scale, **kw):
     return (attn_long_bwd if attn_uses_long(S) else attn_bwd)(qkv, o, o_cls, d_o, d_o_cls, lse, nseq, S, H, scale, **kw)
 
 
+# (embed_dim, num_heads) of the TimeSformer encoders the kernels serve: ViT-B and ViT-L.  head_dim is 64 in every attention kernel, the
+# LayerNorm kernels give each lane embed_dim / 256 float4s of a row (include/pvrl.h) and are instantiated for these widths
+ENCODER_WIDTHS = ((768, 12), (1024, 16))
+
+
+def check_encoder_width(embed_dim, num_heads):
+    """NotImplementedError naming the pair and the supported ones for an encoder size the kernels do not serve, at construction
+    instead of PVRL_EINVAL from inside the first block"""
+    if (int(embed_dim), int(num_heads)) not in ENCODER_WIDTHS:
+        served = ", ".join(f"({c}, {h})" for c, h in ENCODER_WIDTHS)
+        raise NotImplementedError(f"(embed_dim, num_heads) = ({embed_dim}, {num_heads}) is not served by the encoder kernels: the supported "
+                                  f"pairs are {served} (head_dim 64; the LayerNorm kernels map embed_dim / 256 float4s to a lane, so "
+                                  f"e.g. ViT-S's 384 needs a row mapping of its own)")
+
+
 def check_attn_geometry(N, T, scheme, prune_attn, crop_key="DATA.TRAIN_CROP_SIZE", frames_key="DATA.NUM_FRAMES"):
     """The attention kernels' limits for N patches per frame and T frames under TIMESFORMER.ATTENTION_TYPE `scheme`, checked on the host
     before anything is launched: NotImplementedError naming the limit and the key that sets the offending size (`crop_key` /

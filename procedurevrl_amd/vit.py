@@ -395,14 +395,16 @@ class VisionTransformer(nn.Module):
         return x
 
 
-@MODEL_REGISTRY.register()
-class vit_base_patch16_224_develop(nn.Module):
+class _TimeSformer(nn.Module):
+    """The registered TimeSformer models: the reference's wrapper (vit.py:480-509) around VisionTransformer at one (embed_dim, num_heads)"""
+    EMBED_DIM, NUM_HEADS = None, None
+
     def __init__(self, cfg, **kwargs):
         super().__init__()
         self.pretrained = cfg.MODEL.PRETRAINED
         self.model = VisionTransformer(
-            img_size=cfg.DATA.TRAIN_CROP_SIZE, num_classes=cfg.MODEL.NUM_CLASSES, patch_size=16, embed_dim=768,
-            depth=cfg.TIMESFORMER.DEPTH, num_heads=12, mlp_ratio=4, qkv_bias=True,
+            img_size=cfg.DATA.TRAIN_CROP_SIZE, num_classes=cfg.MODEL.NUM_CLASSES, patch_size=16, embed_dim=self.EMBED_DIM,
+            depth=cfg.TIMESFORMER.DEPTH, num_heads=self.NUM_HEADS, mlp_ratio=4, qkv_bias=True,
             norm_layer=partial(nn.LayerNorm, eps=1e-6), drop_rate=0.0, attn_drop_rate=0.0,
             drop_path_rate=cfg.MODEL.DROP_PATH, num_frames=cfg.DATA.NUM_FRAMES,
             attention_type=cfg.TIMESFORMER.ATTENTION_TYPE, label_emb=cfg.TRAIN.LABEL_EMB, mlp=cfg.MODEL.MLP,
@@ -418,6 +420,19 @@ class vit_base_patch16_224_develop(nn.Module):
 
     def forward(self, x, rng=None):
         return self.model(x) if rng is None else self.model(x, rng=rng)
+
+
+@MODEL_REGISTRY.register()
+class vit_base_patch16_224_develop(_TimeSformer):
+    EMBED_DIM, NUM_HEADS = 768, 12
+
+
+@MODEL_REGISTRY.register()
+class vit_large_patch16_224_develop(_TimeSformer):
+    """The same encoder at ViT-L's width (timm's vit_large_patch16_224 key layout); depth from TIMESFORMER.DEPTH as for the base model:
+    ViT-L/16 proper is `MODEL.MODEL_NAME vit_large_patch16_224_develop TIMESFORMER.DEPTH 24`.  The heads, the order transformer and the
+    text tower stay at the label embedding's 512."""
+    EMBED_DIM, NUM_HEADS = 1024, 16
 
 
 def pretrain_loss(pred, teacher_pred, mse, cfg):
