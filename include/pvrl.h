@@ -54,8 +54,11 @@ int pvrl_operand_dtype(void);
  * Replaces nn.Linear forward (vit.py:54-60,75-92,133; tfm_model.py:35-41) and, with the
  * transposed 16-bit weight copy as W, its data gradient.  N % 128 == 0, K % 64 == 0, any M.  bias2 (fp32 [N] or null,
  * PVRL_EPI_RESID_F32 / PVRL_EPI_RESID_16 only) is added after the row scale: x + rs * (o W_e^T + b_e) + b_fc of the fused temporal branch.
- * M <= 192 with K % 256 == 0 (the order / diffusion stack's 36- and 144-row products, tfm_model.py:129-204) runs a few-row kernel whose
- * workgroups split K over their waves (csrc/gemm_nt_skinny.h): same arithmetic up to the order of the fp32 sums over k. */
+ * M <= PVRL_NT_SKINNY_MAX_M with K % PVRL_NT_SKINNY_K == 0 (the order / diffusion stack's 36- and 144-row products, tfm_model.py:129-204)
+ * runs a few-row kernel whose workgroups split K over their waves (csrc/gemm_nt_skinny.h): same arithmetic up to the order of the fp32
+ * sums over k. */
+#define PVRL_NT_SKINNY_MAX_M 192
+#define PVRL_NT_SKINNY_K 256
 int pvrl_gemm_nt_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, int64_t M, int64_t N, int64_t K,
                       int epilogue, const float* bias, const float* rowscale, const void* aux, int64_t aux_ld,
                       int64_t aux_rowmod, void* out0, int64_t ld0, void* out1, int64_t ld1, const float* bias2,
@@ -115,9 +118,10 @@ int pvrl_gemm_tn_into_bf16(const void* P, int64_t ldp, const void* Q, int64_t ld
 /* Several weight gradients of the same backward pass in ONE launch (a transformer block's seven nn.Linear dW,
  * loss.backward(), tools/train_net.py:176-181): the (row slice, 256x256 tile) work items of all problems share the 256 CUs,
  * so every problem is cut into the same small number of slices (pvrl_gemm_tn_grouped_plan_splits) instead of the 7-28 a
- * lone dW needs -- longer reduction loops, less fp32 partial traffic.  1 <= nprob <= 8, every N and K a multiple of
+ * lone dW needs -- longer reduction loops, less fp32 partial traffic.  1 <= nprob <= PVRL_TN_GROUP_MAX, every N and K a multiple of
  * 128 (half tiles are staged with zero columns), M >= 1 (else PVRL_EINVAL: use pvrl_gemm_tn_bf16 per problem).  Semantics per problem as pvrl_gemm_tn_bf16;
  * deterministic.  workspace >= pvrl_gemm_tn_grouped_workspace_bytes(nprob, problems, splits). */
+#define PVRL_TN_GROUP_MAX 8
 typedef struct pvrl_tn_problem {
   const void* P; int64_t ldp;     /* bf16 [M, N] */
   const void* Q; int64_t ldq;     /* bf16 [M, K] */
@@ -183,14 +187,15 @@ typedef struct pvrl_ln_reduce {
 int pvrl_layernorm_bwd_reduce_batched(int n, const pvrl_ln_reduce* items, const float* gscale, float* nonfinite, void* stream);
 
 /* Temporal attention for T = 8 (Block.forward temporal branch, vit.py:129-135 via Attention.forward
- * vit.py:75-92): sequences are 8 consecutive rows of the packed qkv [rows][3*H*64]. */
+ * vit.py:75-92): sequences are 8 consecutive rows of the packed qkv [rows][3*H*PVRL_HEAD_DIM]. */
+#define PVRL_HEAD_DIM 64     /* head_dim of every attention entry point but the pvrl_mvit_* ones */
 int pvrl_attn_t8_fwd(const void* qkv, int64_t ld, int64_t nseq, int64_t H, float scale, void* o, int64_t ldo,
                      void* stream);
 int pvrl_attn_t8_bwd(const void* qkv, int64_t ld, int64_t nseq, int64_t H, float scale, const void* d_o, int64_t ldo,
                      void* dqkv, int64_t ldd, void* stream);
 
-/* General MFMA attention, head_dim 64 (spatial branch vit.py:137-151; nn.MultiheadAttention in
- * tfm_model.py:43-48 with key_padding_mask; CLIP text causal mask).  S <= 416 without masks (the reference takes any crop
+/* General MFMA attention, head_dim PVRL_HEAD_DIM (spatial branch vit.py:137-151; nn.MultiheadAttention in
+ * tfm_model.py:43-48 with key_padding_mask; CLIP text causal mask).  S <= PVRL_ATTN_MAX_S without masks (the reference takes any crop
  * through its pos-embed resize, vit.py:374-386: 224^2 -> 197 tokens, 256^2 -> 257, 320^2 -> 401), S <= 208 with a causal /
  * key-padding mask; PVRL_EINVAL beyond.  The backward of 96 < S <= 224 without masks and with a power-of-two `scale` is ONE
  * persistent kernel (csrc/attn_bwd_fused.hip), that of 16 < S <= 32 contiguous tokens one wave per (sequence, head)
@@ -198,6 +203,7 @@ int pvrl_attn_t8_bwd(const void* qkv, int64_t ld, int64_t nseq, int64_t H, float
  * mode 0: row(seq, j) = seq*S + j.   mode 1 (TimeSformer spatial, seq = b*T + t): token 0 = cls row
  * cls_base + b, token j>=1 = row b*(S-1)*T + (j-1)*T + t; token-0 outputs go to the *_cls side buffers
  * ([nseq] rows).  lse/dvec: [nseq][H][S] fp32. */
+#define PVRL_ATTN_MAX_S 416
 int pvrl_attn_fwd(const void* qkv, int64_t ld, int64_t nseq, int64_t S, int64_t H, int mode, int64_t T,
                   int64_t cls_base, float scale, int causal, const void* key_padding_mask, void* o, void* o_cls,
                   int64_t ldo, float* lse, void* stream);
@@ -206,9 +212,9 @@ int pvrl_attn_bwd(const void* qkv, int64_t ld, int64_t nseq, int64_t S, int64_t 
                   const void* o_cls, const void* d_o, const void* d_o_cls, int64_t ldo, const float* lse, float* dvec,
                   void* dqkv, void* dqkv_cls, int64_t ldd, void* stream);
 
-/* Long-sequence attention, head_dim 64, no masks, any `scale`, 1 <= S <= PVRL_ATTN_LONG_MAX_S (PVRL_EINVAL beyond, nothing launched):
+/* Long-sequence attention, head_dim PVRL_HEAD_DIM, no masks, any `scale`, 1 <= S <= PVRL_ATTN_LONG_MAX_S (PVRL_EINVAL beyond, nothing launched):
  * the joint space-time scheme of the reference (Block.forward, vit.py:124-127: ONE sequence of 1 + N*T tokens per clip) and every
- * sequence longer than the 416 tokens pvrl_attn_fwd keeps in LDS (csrc/attn_long.hip).  K / V are streamed through LDS in tiles of
+ * sequence longer than the PVRL_ATTN_MAX_S tokens pvrl_attn_fwd keeps in LDS (csrc/attn_long.hip).  K / V are streamed through LDS in tiles of
  * PVRL_ATTN_LONG_KT keys with an online softmax (running max and sum in fp32, P rounded to the operand type only as the second
  * product's operand); a workgroup owns PVRL_ATTN_LONG_QT queries of one (sequence, head).  Operands, addressing modes and the *_cls
  * side buffers are those of pvrl_attn_fwd / _bwd (mode 1 with any T).  lse: [nseq][H][S] fp32.
@@ -227,11 +233,12 @@ int pvrl_attn_long_bwd(const void* qkv, int64_t ld, int64_t nseq, int64_t S, int
                        void* workspace, int64_t workspace_bytes, void* stream);
 
 /* The same attention (mode 1 addressing) for the cls query of every sequence ONLY -- the spatial attention of the encoder's LAST block,
- * of whose output only x[:, 0] is read (vit.py:418-421; csrc/attn_cls.hip).  Forward: o_cls [nseq][H*64] and lse[(seq*H + h)*S + 0] (the
+ * of whose output only x[:, 0] is read (vit.py:418-421; csrc/attn_cls.hip).  Forward: o_cls [nseq][H*PVRL_HEAD_DIM] and lse[(seq*H + h)*S + 0] (the
  * other lse entries are not written).  Backward: dO is taken to be zero for every patch query: dK / dV of all S tokens and zeros for the
  * patch tokens' dQ (only with zero_patch_dq != 0: a caller that never reads that third of those rows saves the writes) go to dqkv
  * (token 0's partial row to dqkv_cls[seq], as pvrl_attn_bwd does), dQ of the cls query to dqkv_cls[seq].
- * S >= 2, nseq % T == 0. */
+ * 2 <= S <= PVRL_ATTN_CLS_MAX_S (PVRL_EINVAL beyond), nseq % T == 0. */
+#define PVRL_ATTN_CLS_MAX_S 4096
 int pvrl_attn_cls_fwd(const void* qkv, int64_t ld, int64_t nseq, int64_t S, int64_t H, int64_t T, int64_t cls_base,
                       float scale, void* o_cls, int64_t ldo, float* lse, void* stream);
 int pvrl_attn_cls_bwd(const void* qkv, int64_t ld, int64_t nseq, int64_t S, int64_t H, int64_t T, int64_t cls_base,
@@ -326,7 +333,7 @@ int pvrl_flag_roll(float* flag, float* total, void* stream);
 #define PVRL_MIX_NONE 0      /* the clip is left as it is (its weights are 1 and 0)                                   */
 #define PVRL_MIX_BLEND 1     /* x[b] = x[b] * lam + x[partner] * lam_partner, each product and the sum rounded in fp32  */
 #define PVRL_MIX_CUT 2       /* x[b][:, t0:t1, h0:h1, :] = x[partner][:, t0:t1, h0:h1, :]                              */
-typedef struct {
+typedef struct pvrl_mix_desc {
   int32_t partner;           /* B - 1 - b */
   int32_t kind;              /* PVRL_MIX_* */
   int32_t t0, t1, h0, h1;    /* the cut box as drawn on img_shape[-2:] = (H, W) and applied to a [C, T, H, W] clip as
@@ -379,7 +386,7 @@ int pvrl_view_ensemble(const float* preds, int64_t ldp, const int64_t* clip_ids,
 #define PVRL_RA_SHARPNESS 11     /* Image.blend(ImageFilter.SMOOTH of the frame, frame, c[0])                              */
 #define PVRL_RA_BILINEAR 2       /* resample modes of PVRL_RA_AFFINE: PIL's Image.BILINEAR / Image.BICUBIC                 */
 #define PVRL_RA_BICUBIC 3
-typedef struct {
+typedef struct pvrl_ra_desc {
   int32_t kind;              /* PVRL_RA_* */
   int32_t resample;          /* PVRL_RA_BILINEAR / PVRL_RA_BICUBIC (PVRL_RA_AFFINE only) */
   int32_t iarg[2];           /* integer arguments of the table ops */
@@ -403,8 +410,9 @@ int pvrl_gelu_f32(const float* x, const float* dy, float* out, int64_t n, void* 
 /* ------------------------------------------------------------------------------------------------------------------
  * MViTv2 encoder path (reference lib/models/slowfast_mvit/).  Token matrices: rows [0, B*L) patch tokens
  * ordered (b, t, h, w), rows [B*L, B*L + B) the cls tokens; channel widths padded with zero columns to multiples of 128.
- * Pooled per-head tensors: [B*H][L' + 1][96] bf16 with the cls token LAST.
+ * Pooled per-head tensors: [B*H][L' + 1][PVRL_MVIT_HEAD_DIM] bf16 with the cls token LAST.
  * ------------------------------------------------------------------------------------------------------------------ */
+#define PVRL_MVIT_HEAD_DIM 96   /* head_dim of every MViTv2 block (96/1, 192/2, 384/4, 768/8): "D" in the comments below */
 
 /* im2col of PatchEmbed's Conv3d (stem_helper.py:290-321): frames fp32 [B,Cin,T,H,W] -> bf16 rows (b,to,ho,wo) x ldo columns,
  * column ((c*kt + a)*kh + y)*kw + x = the flatten order of Conv3d.weight; columns >= Cin*kt*kh*kw are zero. */
@@ -426,13 +434,13 @@ int pvrl_layernorm_g_bwd(const void* dy, int64_t lddy, int dy_is_f32, const floa
                          void* dx16, int64_t lddx16, const float* rowscale16, int64_t M, int64_t C, int64_t Cpad,
                          float* dgamma, float* dbeta, void* workspace, int64_t workspace_bytes, void* stream);
 
-/* attention_pool (attention.py:14-48) for mode "conv": depthwise Conv3d(96 ch, kernel 3x3x3, padding 1, stride st,sh,sw, no
- * bias; weight fp32 [96][27]) + LayerNorm(96) on one of q / k / v taken in place from the packed qkv activation (bf16
- * [B*T*Hh*Ww + B][ld], columns col0 + h*96 ..); the cls token skips the conv.  y / conv_out: [B*H][To*Ho*Wo + 1][96] bf16.
+/* attention_pool (attention.py:14-48) for mode "conv": depthwise Conv3d(D ch, kernel 3x3x3, padding 1, stride st,sh,sw, no
+ * bias; weight fp32 [D][27]) + LayerNorm(D) on one of q / k / v taken in place from the packed qkv activation (bf16
+ * [B*T*Hh*Ww + B][ld], columns col0 + h*D ..); the cls token skips the conv.  y / conv_out: [B*H][To*Ho*Wo + 1][D] bf16.
  * conv_out holds the conv output ROUNDED ONCE to the 16-bit operand type (the cls row: the token itself); y is the LayerNorm of
  * the unrounded fp32 conv, while the backward recomputes its LayerNorm statistics (mean, rstd) from conv_out, i.e. from the
  * rounded values -- hand the backward the conv_out the forward wrote, nothing else.
- * Backward writes this tensor's slice of dqkv and ACCUMULATES dw [96][27], dgamma, dbeta; dc_scratch: bf16, size of y;
+ * Backward writes this tensor's slice of dqkv and ACCUMULATES dw [D][27], dgamma, dbeta; dc_scratch: bf16, size of y;
  * workspace >= pvrl_mvit_pool_bwd_workspace_bytes() holds per-workgroup fp32 partials of dw that a second kernel sums in a
  * fixed order (same-address fp32 atomics from 8 XCDs cost ~0.5 us each and made every call ~200 us). */
 int pvrl_mvit_pool_fwd(const void* qkv, int64_t ld, int64_t col0, int64_t B, int64_t H, int64_t T, int64_t Hh, int64_t Ww,
@@ -462,7 +470,7 @@ int pvrl_mvit_maxpool_bwd(const float* x, int64_t ldi, const float* dy, int64_t 
  * the pair hi + lo = out_scale * rel[bh][q][j] (~16 mantissa bits), zeros for j >= kh + kw + kt.  The attention kernels
  * expect out_scale = 1 / scale (the bias joins the q.k score before the scale is applied).
  * Backward: dQ += drel . R (in place on the 16-bit dQ of the attention backward; drel is the fp32 gradient with respect to
- * the UNSCALED rel, [BH][Lq][kh+kw+kt]), dR* ([nrows_*][96]) ACCUMULATED from per-workgroup partials in the workspace
+ * the UNSCALED rel, [BH][Lq][kh+kw+kt]), dR* ([nrows_*][D]) ACCUMULATED from per-workgroup partials in the workspace
  * (>= pvrl_mvit_rel_bwd_workspace_bytes) summed in a fixed order. */
 int64_t pvrl_mvit_rel_width(int64_t kt, int64_t kh, int64_t kw);
 int pvrl_mvit_rel_fwd(const void* Q, int64_t BH, int64_t qt, int64_t qh, int64_t qw, int64_t kt, int64_t kh, int64_t kw,
@@ -476,8 +484,8 @@ int pvrl_mvit_rel_bwd(const float* drel, const void* Q, void* dQ, int64_t BH, in
                       int64_t nrows_t, float* dRh, float* dRw, float* dRt, void* workspace, int64_t workspace_bytes,
                       void* stream);
 
-/* Pooling attention (attention.py:404-442): softmax(scale q k^T + rel bias) v (+ q, residual pooling) for head_dim 96;
- * q [B*H][Lq+1][96], k / v [B*H][kt*kh*kw+1][96]; o / d_o token-major [B*Lq + B][ldo] with column h*96 + d.
+/* Pooling attention (attention.py:404-442): softmax(scale q k^T + rel bias) v (+ q, residual pooling) for head_dim D;
+ * q [B*H][Lq+1][D], k / v [B*H][kt*kh*kw+1][D]; o / d_o token-major [B*Lq + B][ldo] with column h*D + d.
  * relp = the operand form written by pvrl_mvit_rel_fwd with out_scale = 1 / scale.  keymap = the 0/1 matrix
  * E[key][j] (j = h(key), kh + w(key), kh + kw + t(key)) of the key geometry as MFMA tile images, a function of
  * (kt, kh, kw) only: build it once with pvrl_mvit_attn_keymap into pvrl_mvit_attn_keymap_bytes bytes and reuse it.

@@ -1,12 +1,16 @@
 """ctypes binding of libpvrl_hip.so (the C ABI declared in include/pvrl.h).
 
-The prototypes are parsed from the header itself, so the header is the single source of
-truth and `tests/test_cabi.py` can check that every declared symbol is exported.
+The prototypes, the struct layouts and the integer `#define`s (enums, limits) are parsed from the
+header itself, so the header is the single source of truth: `tests/test_cabi.py` checks that every
+declared symbol is exported and the parsed layouts against a C compiler's.
 There is NO fallback: if the library is missing or a call fails, this raises.
 """
 import ctypes
+import functools
 import os
 import re
+
+import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER = os.path.join(_HERE, "..", "include", "pvrl.h")
@@ -27,78 +31,88 @@ def operand_torch_dtype():
     import torch
     return torch.bfloat16 if OPERAND == "bf16" else torch.float16
 
-_CTYPES = {
-    "const void*": ctypes.c_void_p, "void*": ctypes.c_void_p, "void**": ctypes.c_void_p,
-    "const float*": ctypes.c_void_p, "float*": ctypes.c_void_p, "const int32_t*": ctypes.c_void_p, "int*": ctypes.c_void_p, "const void**": ctypes.c_void_p, "const float**": ctypes.c_void_p, "float**": ctypes.c_void_p,
-    "const int64_t*": ctypes.c_void_p, "const pvrl_mix_desc*": ctypes.c_void_p, "const pvrl_ra_desc*": ctypes.c_void_p,
-    "int32_t*": ctypes.c_void_p, "int64_t*": ctypes.c_void_p,
-    "const pvrl_tn_problem*": ctypes.c_void_p, "const pvrl_cast_problem*": ctypes.c_void_p, "const pvrl_nt_problem*": ctypes.c_void_p, "const pvrl_ln_reduce*": ctypes.c_void_p, "const pvrl_rows*": ctypes.c_void_p,
-    "int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double,
-}
-_RET = {"int": ctypes.c_int, "int64_t": ctypes.c_int64}
+
+class PvrlError(RuntimeError):
+    pass
 
 
-def parse_header(path=HEADER):
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
+            "double": ctypes.c_double}
+_TXT = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(HEADER).read(), flags=re.S)      # the header without its comments
+_CONSTANTS = {name: int(v) for name, v in re.findall(r"#define\s+(PVRL_\w+)\s+(-?\d+)", _TXT)}
+
+
+def header_constants():
+    """-> {name: value} of the header's integer `#define PVRL_*` (parsed once, at import)"""
+    return _CONSTANTS
+
+
+def parse_header():
     """-> {name: (restype_name, [(ctype_name, argname), ...])}"""
-    txt = open(path).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    txt = re.sub(r"//[^\n]*", "", txt)
     protos = {}
-    for m in re.finditer(r"\b(int64_t|int)\s+(pvrl_\w+)\s*\(([^)]*)\)\s*;", txt):
-        ret, name, args = m.group(1), m.group(2), m.group(3)
+    for ret, name, args in re.findall(r"\b(int64_t|int)\s+(pvrl_\w+)\s*\(([^)]*)\)\s*;", _TXT):
         parsed = []
         for a in args.split(","):
             a = " ".join(a.split())
             if a in ("void", ""):
                 continue
-            mm = re.match(r"(.*?)(\w+)$", a)
-            ty = mm.group(1).strip().replace(" *", "*")
-            parsed.append((ty, mm.group(2)))
+            ty, argname = re.match(r"(.*?)(\w+)$", a).groups()
+            parsed.append((ty.strip().replace(" *", "*"), argname))
         protos[name] = (ret, parsed)
     return protos
 
 
-def header_constants(path=HEADER):
-    txt = open(path).read()
-    return {m.group(1): int(m.group(2)) for m in re.finditer(r"#define\s+(PVRL_\w+)\s+(-?\d+)", txt)}
+def _ctype(ty, structs=()):
+    """C type spelling -> ctypes type: a scalar of _SCALARS, or c_void_p for a pointer to one, to void or to one of `structs`"""
+    base = ty.replace("const ", "").rstrip("*")
+    if ty.endswith("*") and (base == "void" or base in _SCALARS or base in structs):
+        return ctypes.c_void_p
+    return _SCALARS[ty]
 
 
-class TnProblem(ctypes.Structure):
-    """`pvrl_tn_problem` of include/pvrl.h"""
-    _fields_ = [("P", ctypes.c_void_p), ("ldp", ctypes.c_int64), ("Q", ctypes.c_void_p), ("ldq", ctypes.c_int64),
-                ("M", ctypes.c_int64), ("N", ctypes.c_int64), ("K", ctypes.c_int64), ("beta", ctypes.c_float),
-                ("dW", ctypes.c_void_p), ("dbias", ctypes.c_void_p), ("gscale", ctypes.c_void_p), ("nonfinite", ctypes.c_void_p)]
+def parse_structs(txt=_TXT):
+    """-> {name: [(field, C type, array length or None), ...]} for every `typedef struct name {...} name;` of the header (or of
+    the comment-free text `txt`).  A field is a scalar of _SCALARS, a pointer to one or to void, or a fixed array of those; anything
+    else (bit-fields, nested or anonymous structs, function pointers, other types) raises PvrlError."""
+    structs = {}
+    for m in re.finditer(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;", txt, flags=re.S):
+        tag, body, name = m.groups()
+        if tag != name or "{" in body:
+            raise PvrlError(f"struct {tag}: expected `typedef struct {name} {{ plain fields }} {name};`")
+        structs[name] = []
+        for decl in filter(None, (" ".join(d.split()) for d in body.split(";"))):
+            dm = re.fullmatch(r"((?:const )?\w+ ?\**) ?(\w+(?:\[\d+\])?(?:, ?\w+(?:\[\d+\])?)*)", decl)
+            try:
+                ty = dm.group(1).replace(" ", "").replace("const", "const ")
+                _ctype(ty)
+            except (AttributeError, KeyError):
+                raise PvrlError(f"struct {name}: cannot parse the declaration `{decl}`") from None
+            for item in dm.group(2).replace(" ", "").split(","):
+                field, _, n = item.rstrip("]").partition("[")
+                structs[name].append((field, ty, int(n) if n else None))
+    if len(structs) != len(re.findall(r"\bstruct\b", txt)):
+        raise PvrlError("a `struct` of the header is not of the form `typedef struct name { plain fields } name;`")
+    return structs
 
 
-class NtProblem(ctypes.Structure):
-    """`pvrl_nt_problem` of include/pvrl.h"""
-    _fields_ = [("A", ctypes.c_void_p), ("lda", ctypes.c_int64), ("W", ctypes.c_void_p), ("ldw", ctypes.c_int64),
-                ("M", ctypes.c_int64), ("N", ctypes.c_int64), ("K", ctypes.c_int64), ("bias", ctypes.c_void_p),
-                ("rowscale", ctypes.c_void_p), ("aux", ctypes.c_void_p), ("aux_ld", ctypes.c_int64), ("out0", ctypes.c_void_p),
-                ("ld0", ctypes.c_int64)]
+# every argument type of the header's prototypes (a KeyError here: something other than a pointer or a plain scalar at the boundary)
+_CTYPES = {ty: _ctype(ty, parse_structs()) for _, args in parse_header().values() for ty, _ in args}
 
 
-class LnReduce(ctypes.Structure):
-    """`pvrl_ln_reduce` of include/pvrl.h"""
-    _fields_ = [("part", ctypes.c_void_p), ("M", ctypes.c_int64), ("C", ctypes.c_int64), ("want_sum", ctypes.c_int),
-                ("beta", ctypes.c_float), ("beta_sum", ctypes.c_float), ("dgamma", ctypes.c_void_p), ("dbeta", ctypes.c_void_p),
-                ("dxsum", ctypes.c_void_p)]
+def _struct_class(name):
+    """the ctypes.Structure of the header's struct `name`; setting anything but a field of the header raises AttributeError"""
+    fields = [(f, _ctype(ty) * n if n else _ctype(ty)) for f, ty, n in parse_structs()[name]]
+    return type(name, (ctypes.Structure,), {"_fields_": fields, "__slots__": (), "__doc__": f"`{name}` of include/pvrl.h"})
 
 
-class Rows(ctypes.Structure):
-    """`pvrl_rows` of include/pvrl.h: rows [0, rows16) in the 16-bit matrix `lo`, the rest in the fp32 matrix `hi`"""
-    _fields_ = [("lo", ctypes.c_void_p), ("ldlo", ctypes.c_int64), ("hi", ctypes.c_void_p), ("ldhi", ctypes.c_int64),
-                ("rows16", ctypes.c_int64)]
+def struct_dtype(name):
+    """the numpy structured dtype of the header's struct `name`: the C layout, with explicit offsets and itemsize"""
+    return np.dtype(_struct_class(name))
 
 
-class CastProblem(ctypes.Structure):
-    """`pvrl_cast_problem` of include/pvrl.h"""
-    _fields_ = [("inp", ctypes.c_void_p), ("out", ctypes.c_void_p), ("out_t", ctypes.c_void_p), ("R", ctypes.c_int64),
-                ("C", ctypes.c_int64)]
-
-
-class PvrlError(RuntimeError):
-    pass
+TnProblem, NtProblem, LnReduce = _struct_class("pvrl_tn_problem"), _struct_class("pvrl_nt_problem"), _struct_class("pvrl_ln_reduce")
+# pvrl_rows: rows [0, rows16) in the 16-bit matrix `lo`, the rest in the fp32 matrix `hi`
+Rows, CastProblem = _struct_class("pvrl_rows"), _struct_class("pvrl_cast_problem")
 
 
 class _Lib:
@@ -115,9 +129,9 @@ class _Lib:
         self._fn = {}
         for name, (ret, args) in self.protos.items():
             fn = getattr(self.cdll, name)  # AttributeError -> loud failure on a missing export
-            fn.restype = _RET[ret]
+            fn.restype = _SCALARS[ret]
             fn.argtypes = [_CTYPES[t] for t, _ in args]
-            self._fn[name] = (fn, ret == "int")
+            self._fn[name] = (fn, ret == "int", len(args))
         for k, v in header_constants().items():
             setattr(self, k, v)
         built = self.cdll.pvrl_operand_dtype()
@@ -125,18 +139,15 @@ class _Lib:
             raise PvrlError(f"{LIB_PATH} was built for operand code {built}, PVRL_OPERAND={OPERAND}")
 
     def call(self, name, *args):
-        fn, is_status = self._fn[name]
+        fn, is_status, nargs = self._fn[name]
+        if len(args) != nargs:     # ctypes itself refuses too few arguments but passes any number too many
+            raise PvrlError(f"{name} takes {nargs} arguments (include/pvrl.h), {len(args)} given")
         rc = fn(*args)
         if is_status and rc != 0:
             raise PvrlError(f"{name} failed with status {rc}")
         return rc
 
 
-_lib = None
-
-
+@functools.lru_cache(maxsize=None)
 def lib():
-    global _lib
-    if _lib is None:
-        _lib = _Lib()
-    return _lib
+    return _Lib()

@@ -212,7 +212,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p, int 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int S = p.mp.S;
   const int nqb = NQB > 0 ? NQB : (S + 31) >> 5;
-  const int HD = p.H * 64;
+  const int HD = p.H * PVRL_HEAD_DIM;
   const int n = lane & 31, g = lane >> 5;
   const bool keywave = wave < nqb;
   const float c = p.scale * 1.4426950408889634f;

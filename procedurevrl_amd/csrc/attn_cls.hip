@@ -54,7 +54,7 @@ __global__ __launch_bounds__(64 * AC_WAVES) void attn_cls_fwd_kernel(AttnCls p) 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int item = min((int)blockIdx.x * AC_WAVES + wave, p.nseq * p.H - 1);     // (a clamped wave repeats the last item: same stores)
   const int seq = item / p.H, h = item - seq * p.H;
-  const int S = p.mp.S, HD = p.H * 64;
+  const int S = p.mp.S, HD = p.H * PVRL_HEAD_DIM;
   const int c = lane & 7, kg = lane >> 3;
   const SeqRows sr = seq_rows(p.mp, seq);
   float q8[8];
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(64 * AC_WAVES) void attn_cls_bwd_kernel(AttnCls p) 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int item = min((int)blockIdx.x * AC_WAVES + wave, p.nseq * p.H - 1);
   const int seq = item / p.H, h = item - seq * p.H;
-  const int S = p.mp.S, HD = p.H * 64;
+  const int S = p.mp.S, HD = p.H * PVRL_HEAD_DIM;
   const int c = lane & 7, kg = lane >> 3;
   const SeqRows sr = seq_rows(p.mp, seq);
   float q8[8], do8[8];
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(64 * AC_WAVES) void attn_cls_bwd_kernel(AttnCls p) 
 }
 
 int check(const AttnCls& p) {
-  if (!p.qkv || !p.lse || p.H <= 0 || p.nseq < 0 || p.mp.S <= 1 || p.mp.S > 4096) return PVRL_EINVAL;
+  if (!p.qkv || !p.lse || p.H <= 0 || p.nseq < 0 || p.mp.S <= 1 || p.mp.S > PVRL_ATTN_CLS_MAX_S) return PVRL_EINVAL;
   if (p.mp.T <= 0 || (p.nseq % p.mp.T) || (p.ld % 8) || ((uintptr_t)p.qkv & 15)) return PVRL_EINVAL;
   return PVRL_OK;
 }

@@ -13,6 +13,7 @@
 //          vit.py:139-141 differ after attention and are averaged later, vit.py:147-149).
 #pragma once
 #include "common.h"
+#include "../../include/pvrl.h"
 
 struct SeqMap {
   int mode, S, T;
@@ -29,6 +30,7 @@ constexpr int ATT_MAX_TILES = 13;               // S <= 208
 constexpr int ATT_ROWS = ATT_MAX_TILES * 16;    // 208
 constexpr int ATT_ROWS_PAD = 224;               // rounded to 32 for the K=32 MFMA steps
 constexpr int ATT_ROWS_LONG = 26 * 16;          // 416: the long-sequence instantiations of the same kernels (NKT = 17, 26)
+static_assert(ATT_ROWS_LONG == PVRL_ATTN_MAX_S, "include/pvrl.h states the limit the callers read");
 constexpr int ATT_RM_BYTES = ATT_ROWS_PAD * 128;  // row-major [224][64] bf16 tile, 28 KiB
 constexpr int ATT_BL_BYTES = ATT_ROWS_PAD * 128;  // blocked [56][4][4][16] bf16 tile, 28 KiB
 
@@ -144,6 +146,7 @@ __device__ __forceinline__ unsigned pack_opx2(float a, float b) {
 
 // ---- head_dim 96 (MViTv2): 32-row tiles of 6 sixteen-column blocks, shared by attn_pool.hip and mvit_rel.hip
 constexpr int PB_D = 96, NCB = 6;
+static_assert(PB_D == PVRL_MVIT_HEAD_DIM, "include/pvrl.h states the head_dim the callers read");
 // blocked [rows][96] bf16 tile: contiguous [4 rows][16 cols] 128-byte blocks, pairwise block swizzle
 __device__ __forceinline__ int pb_off(int row, int col) {
   const int rb = row >> 2;

@@ -65,7 +65,7 @@ __global__ __launch_bounds__(NT, 2) void attn_long_fwd_kernel(AttnArgs p) {
   __shared__ __attribute__((aligned(16))) char smem[4 * TILE];   // [buffer][K | V]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int S = p.mp.S, HD = p.H * 64;
+  const int S = p.mp.S, HD = p.H * PVRL_HEAD_DIM;
   const Item it = item_of(p, (S + QT - 1) / QT);
   const int seq = it.seq, h = it.h;
   const SeqRows sr = seq_rows(p.mp, seq);
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(NT, 2) void attn_long_bwd_q_kernel(AttnArgs p) {
   __shared__ __attribute__((aligned(16))) char smem[4 * TILE];   // [buffer][K | V]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int S = p.mp.S, HD = p.H * 64;
+  const int S = p.mp.S, HD = p.H * PVRL_HEAD_DIM;
   const Item it = item_of(p, (S + QT - 1) / QT);
   const int seq = it.seq, h = it.h;
   const SeqRows sr = seq_rows(p.mp, seq);
@@ -283,7 +283,7 @@ __global__ __launch_bounds__(NT, 2) void attn_long_bwd_kv_kernel(AttnArgs p) {
   float* stats = reinterpret_cast<float*>(smem + 4 * TILE);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int S = p.mp.S, HD = p.H * 64;
+  const int S = p.mp.S, HD = p.H * PVRL_HEAD_DIM;
   const Item it = item_of(p, (S + QT - 1) / QT);
   const int seq = it.seq, h = it.h;
   const SeqRows sr = seq_rows(p.mp, seq);

@@ -107,7 +107,7 @@ __global__ __launch_bounds__(64 * NW, NKT > 13 ? 2 : (NW + 1) / 2) void attn_fwd
   const int seq = (xj / p.H) * 8 + (blockIdx.x & 7), h = xj % p.H;
   if (seq >= p.nseq) return;
   const int S = SC ? SC : p.mp.S;     // SC: the sequence length as a compile-time constant (0 = run time)
-  const int HD = p.H * 64;
+  const int HD = p.H * PVRL_HEAD_DIM;
   const SeqRows sr = seq_rows(p.mp, seq);
   constexpr int MAXT = (NKT + NW - 1) / NW;   // query tiles per wave
   const int q4 = lane >> 4, i = lane & 15;
@@ -235,7 +235,7 @@ __global__ __launch_bounds__(64 * NW, NKT > 13 ? 2 : (NW + 1) / 2) void attn_bwd
   const int seq = (xj / p.H) * 8 + (blockIdx.x & 7), h = xj % p.H;
   if (seq >= p.nseq) return;
   const int S = SC ? SC : p.mp.S;     // SC: the sequence length as a compile-time constant (0 = run time)
-  const int HD = p.H * 64;
+  const int HD = p.H * PVRL_HEAD_DIM;
   const SeqRows sr = seq_rows(p.mp, seq);
   constexpr int MAXT = (NKT + NW - 1) / NW;   // query tiles per wave
   const int q4 = lane >> 4, i = lane & 15;
@@ -371,7 +371,7 @@ __global__ __launch_bounds__(64 * NW, NKT > 13 ? 2 : (NW + 1) / 2) void attn_bwd
   const int seq = (xj / p.H) * 8 + (blockIdx.x & 7), h = xj % p.H;
   if (seq >= p.nseq) return;
   const int S = SC ? SC : p.mp.S;     // SC: the sequence length as a compile-time constant (0 = run time)
-  const int HD = p.H * 64;
+  const int HD = p.H * PVRL_HEAD_DIM;
   const SeqRows sr = seq_rows(p.mp, seq);
   constexpr int MAXT = (NKT + NW - 1) / NW;   // key tiles per wave
   const int q4 = lane >> 4, i = lane & 15;

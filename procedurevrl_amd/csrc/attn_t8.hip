@@ -39,7 +39,7 @@ __global__ __launch_bounds__(256) void attn_t8_kernel(const op_t* __restrict__ q
   const int task = blockIdx.x * 4 + wave;
   const bool valid = task < ntask;
   const int seq = valid ? task / H : 0, h = valid ? task - seq * H : 0;
-  const int HD = H * 64;
+  const int HD = H * PVRL_HEAD_DIM;
   const int r8 = lane >> 3, c8 = lane & 7;
   const long grow = (long)seq * 8 + r8;
   {

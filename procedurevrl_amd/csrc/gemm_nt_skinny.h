@@ -15,7 +15,8 @@ namespace {
 
 constexpr int SK_MT = 3;          // 16-row tiles per pass (48 rows); more rows: blockIdx.y passes
 constexpr int SK_NW = 8;
-constexpr int SK_MAX_M = 192;
+constexpr int SK_MAX_M = PVRL_NT_SKINNY_MAX_M;
+static_assert(32 * SK_NW == PVRL_NT_SKINNY_K, "include/pvrl.h states the rule the callers read");
 
 template <int EPI>
 __global__ __launch_bounds__(64 * SK_NW) void gemm_nt_skinny_kernel(GemmNT p) {

@@ -424,7 +424,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_rt8_kernel(GemmTN p) {
 // XCDs in contiguous chunks.  A Linear's dW has 9-36 tiles of 256x256; alone, each needs 7-28 row slices to fill 256 CUs
 // (short reduction loops, 67 MB of fp32 partials per call); a transformer block's seven dW together have 153 tiles, so 5
 // slices give 765 equal work items = 2.99 rounds of 256, with 5x longer loops and 2.3x less partial traffic.
-constexpr int TN_GROUP_MAX = 8;
+constexpr int TN_GROUP_MAX = PVRL_TN_GROUP_MAX;
 struct TnGroup {
   int nprob, total, per_xcd;
   int first[TN_GROUP_MAX + 1];     // first global pair index of each problem

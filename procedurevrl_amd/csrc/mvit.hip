@@ -12,7 +12,7 @@
 
 namespace {
 
-constexpr int HD = 96;   // head_dim of every MViTv2 block (96/1, 192/2, 384/4, 768/8)
+constexpr int HD = PVRL_MVIT_HEAD_DIM;   // head_dim of every MViTv2 block (96/1, 192/2, 384/4, 768/8)
 
 inline unsigned grid_for(long total, int per_block = 256) {
   long b = (total + per_block - 1) / per_block;

@@ -17,7 +17,9 @@ mode, `x_orig` in 'pair' / 'elem').  Kept on purpose, as the reference has them:
 import numpy as np
 import torch
 
-NONE, BLEND, CUT = 0, 1, 2                       # PVRL_MIX_* of include/pvrl.h
+from ._lib import header_constants, struct_dtype
+
+NONE, BLEND, CUT = (header_constants()["PVRL_MIX_" + k] for k in ("NONE", "BLEND", "CUT"))
 EPIC_WIDTHS = {"verb": 97, "noun": 300}          # mixup_target's one-hot widths for the EPIC-Kitchens label dict
 
 
@@ -64,12 +66,12 @@ class MixPlan:
         return not bool((self.kind != NONE).any())
 
     def descriptors(self):
-        """int32 [B, 8]: the `pvrl_mix_desc` array (the two weights as the bits of their fp32 values)."""
-        d = np.zeros((self.batch_size, 8), dtype=np.int32)
-        d[:, 0], d[:, 1], d[:, 2:6] = self.partner, self.kind, self.box
-        d[:, 6] = self.lam.astype(np.float32).view(np.int32)
-        d[:, 7] = self.lam_partner.astype(np.float32).view(np.int32)
-        return d
+        """int32 [B, 8]: the `pvrl_mix_desc` array, filled by field name and viewed as int32 (the two weights show as the
+        bits of their fp32 values)."""
+        d = np.zeros(self.batch_size, dtype=struct_dtype("pvrl_mix_desc"))
+        d["partner"], d["kind"], d["lam"], d["lam_partner"] = self.partner, self.kind, self.lam, self.lam_partner
+        d["t0"], d["t1"], d["h0"], d["h1"] = np.asarray(self.box).reshape(-1, 4).T
+        return d.view(np.int32).reshape(self.batch_size, 8)
 
     def device_descriptors(self, device):
         """the descriptors on `device` (uploaded once per device, asynchronously from pinned memory)"""

@@ -28,7 +28,7 @@ from .vit import VisionTransformer as _StepMatchingModel, trunc_normal_
 
 OP16 = ops.OP16
 F32 = torch.float32
-HD = 96
+HD = om.HD          # PVRL_MVIT_HEAD_DIM of include/pvrl.h
 
 
 # ------------------------------------------------------------------------------------------------ geometry

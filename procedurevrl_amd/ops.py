@@ -10,6 +10,9 @@ import torch
 
 from ._lib import lib, PvrlError, header_constants, operand_torch_dtype
 
+_HC = header_constants()         # the limits and sizes both sides of the C ABI use are stated once, in include/pvrl.h
+NT_SKINNY_MAX_M, NT_SKINNY_K, TN_GROUP_MAX = _HC["PVRL_NT_SKINNY_MAX_M"], _HC["PVRL_NT_SKINNY_K"], _HC["PVRL_TN_GROUP_MAX"]
+HEAD_DIM = _HC["PVRL_HEAD_DIM"]
 OP16 = operand_torch_dtype()     # the library flavour's 16-bit operand type: torch.bfloat16 (default) or torch.float16
 F32 = torch.float32
 
@@ -83,6 +86,11 @@ def _ld(t):
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
 
 
+def _ptr_ld(t):
+    """(pointer, leading dimension) of an optional 2-D tensor: (None, 0) when it is absent"""
+    return (None, 0) if t is None else (_ptr(t), _ld(t))
+
+
 # ----------------------------------------------------------------------------------------
 # GEMMs
 # ----------------------------------------------------------------------------------------
@@ -102,11 +110,11 @@ def gemm_nt(A, W, epi, bias=None, rowscale=None, aux=None, aux_rowmod=0, out0=No
     if two and out1 is None:
         out1 = torch.empty((M, N), device=A.device, dtype=OP16)
     # (few-row problems run gemm_nt_skinny_kernel, csrc/gemm_nt_skinny.h: their own family in the bench's per-kernel timing)
-    fam = "gemm_nt_skinny<" if (M <= 192 and K % 256 == 0) else "gemm_nt_kernel<"
+    fam = "gemm_nt_skinny<" if (M <= NT_SKINNY_MAX_M and K % NT_SKINNY_K == 0) else "gemm_nt_kernel<"
     _timed(fam + _EPI_NAMES[epi] + ">", 2.0 * M * N * K, lambda: L.call(
         "pvrl_gemm_nt_bf16", _ptr(A), _ld(A), _ptr(W), _ld(W), M, N, K, epi, _ptr(bias), _ptr(rowscale),
-        _ptr(aux), _ld(aux) if aux is not None else 0, aux_rowmod, _ptr(out0), _ld(out0),
-        _ptr(out1), _ld(out1) if out1 is not None else 0, _ptr(bias2), _stream()))
+        *_ptr_ld(aux), aux_rowmod, _ptr(out0), _ld(out0),
+        *_ptr_ld(out1), _ptr(bias2), _stream()))
     return (out0, out1) if two else out0
 
 
@@ -132,7 +140,7 @@ def gemm_nt_batched(problems, epi):
         a.A, a.lda, a.W, a.ldw, a.M, a.N, a.K = A.data_ptr(), _ld(A), W.data_ptr(), _ld(W), M, N, K
         a.bias = None if bias is None else bias.data_ptr()
         a.rowscale = None if rs is None else rs.data_ptr()
-        a.aux, a.aux_ld = (None, 0) if aux is None else (aux.data_ptr(), _ld(aux))
+        a.aux, a.aux_ld = _ptr_ld(aux)
         a.out0, a.ld0 = out0.data_ptr(), _ld(out0)
         outs.append(out0)
         flops += 2.0 * M * N * K
@@ -168,7 +176,7 @@ def cls_linear(X, W, bias=None, gelu=False, rowscale=None, biasscale=None, aux=N
     nbytes = L.call("pvrl_cls_linear_f32_workspace_bytes", M, N, K)
     ws = workspace(nbytes, X.device, "cls_part") if nbytes else None
     L.call("pvrl_cls_linear_f32", _ptr(X), _ld(X), _ptr(W), _ld(W), _ptr(bias), M, N, K, 1 if gelu else 0, _ptr(rowscale),
-           _ptr(biasscale), _ptr(aux), _ld(aux) if aux is not None else 0, _ptr(out), _ld(out), None, None, 0, _ptr(ws),
+           _ptr(biasscale), *_ptr_ld(aux), _ptr(out), _ld(out), None, None, 0, _ptr(ws),
            ws.numel() if ws is not None else 0, _stream())
     return out
 
@@ -230,9 +238,6 @@ def gemm_tn_into(P, Q, dW, n_valid, k_valid, dbias=None, beta=0.0, beta_bias=0.0
         "pvrl_gemm_tn_into_bf16", _ptr(P), _ld(P), _ptr(Q), _ld(Q), M, N, K, splits, float(beta), _ptr(dW), dW.stride(0),
         n_valid, k_valid, _ptr(dbias), float(beta_bias), _ptr(ws), ws.numel(), _ptr(gscale), _ptr(nonfinite), _stream()))
     return dW
-
-
-TN_GROUP_MAX = 8
 
 
 def gemm_tn_grouped(problems, ws_tag="tn_group"):
@@ -299,8 +304,8 @@ class SplitRows:
     def c_rows(self):
         from ._lib import Rows
         r = Rows()
-        r.lo, r.ldlo = (self.lo.data_ptr(), _ld(self.lo)) if self.lo is not None else (None, 0)
-        r.hi, r.ldhi = (self.hi.data_ptr(), _ld(self.hi)) if self.hi is not None else (None, 0)
+        r.lo, r.ldlo = _ptr_ld(self.lo)
+        r.hi, r.ldhi = _ptr_ld(self.hi)
         r.rows16 = self.n_lo
         return r
 
@@ -314,9 +319,8 @@ def layernorm_fwd(x, gamma, beta, eps, out_dtype=OP16, out=None, save_stats=True
             out = torch.empty((M, C), device=x.device, dtype=out_dtype)
         mean = torch.empty(M, device=x.device, dtype=F32) if save_stats else None
         rstd = torch.empty(M, device=x.device, dtype=F32) if save_stats else None
-        L.call("pvrl_layernorm_fwd_split", _ptr(x.lo), _ld(x.lo) if x.lo is not None else 0, x.n_lo, _ptr(x.hi),
-               _ld(x.hi) if x.hi is not None else 0, _ptr(gamma), _ptr(beta), float(eps), _ptr(out), _ld(out),
-               1 if out.dtype == F32 else 0, _ptr(mean), _ptr(rstd), M, C, _stream())
+        L.call("pvrl_layernorm_fwd_split", *_ptr_ld(x.lo), x.n_lo, *_ptr_ld(x.hi), _ptr(gamma), _ptr(beta), float(eps),
+               _ptr(out), _ld(out), 1 if out.dtype == F32 else 0, _ptr(mean), _ptr(rstd), M, C, _stream())
         return out, mean, rstd
     _chk2d(x, F32)
     M, C = x.shape
@@ -365,14 +369,14 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, dgamma, dbeta, dx_in=None, dx_out=No
             tgt = torch.empty_like(dxsum)
     head = (_ptr(dy), _ld(dy), 1 if dy.dtype == F32 else 0)
     tail = (float(beta_acc), None if deferred else _ptr(dgamma), None if deferred else _ptr(dbeta), _ptr(ws), ws.numel(), M, C,
-            _ptr(dxs), _ld(dxs) if dxs is not None else 0, _ptr(dxs_scale), dxs.shape[0] if dxs is not None else 0, _ptr(tgt),
+            *_ptr_ld(dxs), _ptr(dxs_scale), dxs.shape[0] if dxs is not None else 0, _ptr(tgt),
             None if deferred else _ptr(gscale), None if deferred else _ptr(nonfinite), _stream())
     if split:
         L.call("pvrl_layernorm_bwd_split", *head, ctypes.addressof(xr), _ptr(mean), _ptr(rstd), _ptr(gamma),
                ctypes.addressof(dir_) if dir_ is not None else None, ctypes.addressof(dor), *tail)
     else:
-        L.call("pvrl_layernorm_bwd", *head, _ptr(x), _ld(x), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(dx_in),
-               _ld(dx_in) if dx_in is not None else 0, _ptr(dx_out), _ld(dx_out), *tail)
+        L.call("pvrl_layernorm_bwd", *head, _ptr(x), _ld(x), _ptr(mean), _ptr(rstd), _ptr(gamma), *_ptr_ld(dx_in),
+               _ptr(dx_out), _ld(dx_out), *tail)
     if tgt is not dxsum:
         dxsum.mul_(float(dxsum_beta)).add_(tgt)
     if deferred:
@@ -403,7 +407,7 @@ def attn_t8_fwd(qkv, nseq, H, scale, out=None):
     L = lib()
     _chk2d(qkv, OP16)
     if out is None:
-        out = torch.empty((nseq * 8, H * 64), device=qkv.device, dtype=OP16)
+        out = torch.empty((nseq * 8, H * HEAD_DIM), device=qkv.device, dtype=OP16)
     L.call("pvrl_attn_t8_fwd", _ptr(qkv), _ld(qkv), nseq, H, float(scale), _ptr(out), _ld(out), _stream())
     return out
 
@@ -412,7 +416,7 @@ def attn_t8_bwd(qkv, d_o, nseq, H, scale, dqkv=None):
     L = lib()
     _chk2d(qkv, OP16); _chk2d(d_o, OP16)
     if dqkv is None:
-        dqkv = torch.empty((nseq * 8, 3 * H * 64), device=qkv.device, dtype=OP16)
+        dqkv = torch.empty((nseq * 8, 3 * H * HEAD_DIM), device=qkv.device, dtype=OP16)
     L.call("pvrl_attn_t8_bwd", _ptr(qkv), _ld(qkv), nseq, H, float(scale), _ptr(d_o), _ld(d_o), _ptr(dqkv), _ld(dqkv),
            _stream())
     return dqkv
@@ -422,9 +426,9 @@ def _attn_fwd_outputs(qkv, nseq, S, H, mode, cls_base, o, o_cls, lse):
     """checks and allocates what attn_fwd / attn_long_fwd write -> (o, o_cls, lse)"""
     _chk2d(qkv, OP16)
     if o is None:
-        o = torch.empty((nseq * S if mode == 0 else cls_base, H * 64), device=qkv.device, dtype=OP16)
+        o = torch.empty((nseq * S if mode == 0 else cls_base, H * HEAD_DIM), device=qkv.device, dtype=OP16)
     if mode == 1 and o_cls is None:
-        o_cls = torch.empty((nseq, H * 64), device=qkv.device, dtype=OP16)
+        o_cls = torch.empty((nseq, H * HEAD_DIM), device=qkv.device, dtype=OP16)
     if lse is None:
         lse = torch.empty((nseq, H, S), device=qkv.device, dtype=F32)
     if o_cls is not None:
@@ -462,7 +466,7 @@ def attn_cls_fwd(qkv, nseq, S, H, scale, T, cls_base, o_cls=None, lse=None):
     of every (sequence, head) valid): the encoder's last block (pvrl_attn_cls_fwd)"""
     _chk2d(qkv, OP16)
     if o_cls is None:
-        o_cls = torch.empty((nseq, H * 64), device=qkv.device, dtype=OP16)
+        o_cls = torch.empty((nseq, H * HEAD_DIM), device=qkv.device, dtype=OP16)
     if lse is None:
         lse = torch.empty((nseq, H, S), device=qkv.device, dtype=F32)
     lib().call("pvrl_attn_cls_fwd", _ptr(qkv), _ld(qkv), nseq, S, H, T, cls_base, float(scale), _ptr(o_cls), _ld(o_cls), _ptr(lse),
@@ -492,12 +496,9 @@ def attn_bwd(qkv, o, o_cls, d_o, d_o_cls, lse, nseq, S, H, scale, mode=0, T=1, c
 
 
 # the long-sequence kernels' tiles and limits (include/pvrl.h; read from the header, so importing them needs no built library)
-_HC = header_constants()
 ATTN_LONG_KT, ATTN_LONG_QT, ATTN_LONG_MAX_S = _HC["PVRL_ATTN_LONG_KT"], _HC["PVRL_ATTN_LONG_QT"], _HC["PVRL_ATTN_LONG_MAX_S"]
-ATTN_MAX_S = 416      # the longest sequence pvrl_attn_fwd / _bwd keep in LDS (csrc/attn_common.h, ATT_ROWS_LONG)
-
-
-ATTN_CLS_MAX_S = 4096  # the longest sequence pvrl_attn_cls_fwd / _bwd take (csrc/attn_cls.hip)
+ATTN_MAX_S = _HC["PVRL_ATTN_MAX_S"]      # the longest sequence pvrl_attn_fwd / _bwd keep in LDS (csrc/attn_common.h, ATT_ROWS_LONG)
+ATTN_CLS_MAX_S = _HC["PVRL_ATTN_CLS_MAX_S"]  # the longest sequence pvrl_attn_cls_fwd / _bwd take (csrc/attn_cls.hip)
 
 
 def attn_family(S):
@@ -795,7 +796,8 @@ def cast_weights_multi(items):
     for a, (w, out, out_t) in zip(arr, items):
         assert w.dtype == F32 and w.dim() == 2 and w.is_contiguous() and out.is_contiguous() and out.dtype == OP16
         assert out_t is None or (out_t.is_contiguous() and out_t.dtype == OP16)
-        a.inp, a.out, a.out_t = w.data_ptr(), out.data_ptr(), (None if out_t is None else out_t.data_ptr())
+        setattr(a, "in", w.data_ptr())      # the header's field name is a Python keyword
+        a.out, a.out_t = out.data_ptr(), (None if out_t is None else out_t.data_ptr())
         a.R, a.C = w.shape
     lib().call("pvrl_cast_weights_multi_bf16", len(items), ctypes.addressof(arr), _stream())
 
@@ -807,7 +809,7 @@ def group_reduce(x, groups, G, scale=None, alpha=1.0, resid=None, out=None, out_
     if out is None:
         out = torch.empty((groups, C), device=x.device, dtype=out_dtype)
     L.call("pvrl_group_reduce", _ptr(x), 1 if x.dtype == F32 else 0, _ld(x), groups, G, C, _ptr(scale), float(alpha),
-           _ptr(resid), _ld(resid) if resid is not None else 0, _ptr(out), 1 if out.dtype == F32 else 0, _ld(out),
+           *_ptr_ld(resid), _ptr(out), 1 if out.dtype == F32 else 0, _ld(out),
            _stream())
     return out
 
@@ -854,8 +856,7 @@ def kl_topk(pred, teacher, topk, grad_scale=None, want_target=False):
     dpred = torch.empty_like(pred) if grad_scale is not None else None
     target = torch.empty_like(pred) if want_target else None
     L.call("pvrl_kl_topk", _ptr(pred), _ld(pred), _ptr(teacher), _ld(teacher), rows, K, topk,
-           float(grad_scale if grad_scale is not None else 0.0), _ptr(row_loss), _ptr(dpred),
-           _ld(dpred) if dpred is not None else 0, _ptr(target), _ld(target) if target is not None else 0, _stream())
+           float(grad_scale if grad_scale is not None else 0.0), _ptr(row_loss), *_ptr_ld(dpred), *_ptr_ld(target), _stream())
     return row_loss, dpred, target
 
 
@@ -952,9 +953,8 @@ def soft_ce(x, target=None, labels=None, plan=None, grad_scale=None):
         on, off = plan.on, plan.off
     row_loss = torch.empty(rows, device=x.device, dtype=F32)
     dx = torch.empty_like(x) if grad_scale is not None else None
-    L.call("pvrl_soft_ce", _ptr(x), _ld(x), rows, K, _ptr(target), _ld(target) if target is not None else 0, _ptr(lab),
-           _ptr(desc), float(on), float(off), float(grad_scale if grad_scale is not None else 0.0), _ptr(row_loss), _ptr(dx),
-           _ld(dx) if dx is not None else 0, _stream())
+    L.call("pvrl_soft_ce", _ptr(x), _ld(x), rows, K, *_ptr_ld(target), _ptr(lab),
+           _ptr(desc), float(on), float(off), float(grad_scale if grad_scale is not None else 0.0), _ptr(row_loss), *_ptr_ld(dx), _stream())
     return row_loss, dx
 
 

@@ -3,11 +3,11 @@ Same rules as ops.py: device tensors in, device tensors out, raw pointers to lib
 no PyTorch compute fallback.  Pooled per-head tensors are [B*H, L+1, 96] bf16 with the cls token LAST."""
 import torch
 
-from ._lib import lib
-from .ops import OP16, F32, _ptr, _stream
+from ._lib import lib, header_constants
+from .ops import OP16, F32, _ptr, _stream, workspace
 
 I32 = torch.int32
-HD = 96
+HD = header_constants()["PVRL_MVIT_HEAD_DIM"]
 
 
 def pad128(c):
@@ -48,7 +48,6 @@ def ln_bwd(dy, x, C, mean, rstd, gamma, dgamma, dbeta, dres=None, Cpad=None, wan
     dx = torch.empty((M, Cpad), device=x.device, dtype=F32)
     dx16 = torch.empty((M, Cpad), device=x.device, dtype=OP16) if want16 else None
     assert dy.dtype in (F32, OP16) and dy.stride(1) == 1 and dgamma.dtype == F32 and dgamma.is_contiguous()
-    from .ops import workspace
     ws = workspace(L.call("pvrl_layernorm_g_bwd_workspace_bytes", M, C), x.device, "mvit_ln_g")
     L.call("pvrl_layernorm_g_bwd", _ptr(dy), dy.stride(0), int(dy.dtype == F32), _ptr(x), x.stride(0), _ptr(mean),
            _ptr(rstd), _ptr(gamma), _ptr(dres), dres.stride(0) if dres is not None else 0, _ptr(dx), dx.stride(0),
@@ -77,7 +76,6 @@ def pool_bwd(dy, conv_out, qkv, dqkv, col0, B, H, thw, stride, w, gamma, eps, dw
     L = lib()
     scratch = torch.empty_like(conv_out)
     assert dy.dtype == OP16 and dy.is_contiguous() and dw.is_contiguous() and dw.dtype == F32
-    from .ops import workspace
     ws = workspace(L.call("pvrl_mvit_pool_bwd_workspace_bytes"), dy.device, "mvit_pool_bwd")
     L.call("pvrl_mvit_pool_bwd", _ptr(dy), _ptr(conv_out), _ptr(qkv), _ptr(dqkv), qkv.stride(0), col0, B, H, *thw,
            *stride, _ptr(w), _ptr(gamma), float(eps), _ptr(scratch), _ptr(dw), _ptr(dgamma), _ptr(dbeta), _ptr(ws),
@@ -164,7 +162,6 @@ def keymap(k_thw, device):
 
 def rel_bwd(drel, Q, dQ, BH, q_thw, k_thw, Rh, Rw, Rt, ih, iw, it, dRh, dRw, dRt):
     L = lib()
-    from .ops import workspace
     ws = workspace(L.call("pvrl_mvit_rel_bwd_workspace_bytes", BH, *q_thw, *k_thw), drel.device, "mvit_rel_bwd")
     assert dRh.is_contiguous() and dRw.is_contiguous() and dRt.is_contiguous()
     L.call("pvrl_mvit_rel_bwd", _ptr(drel), _ptr(Q), _ptr(dQ), BH, *q_thw, *k_thw, _ptr(Rh), _ptr(Rw), _ptr(Rt), _ptr(ih),
@@ -194,7 +191,6 @@ def attn_bwd(q, k, v, relp, B, H, Lq, k_thw, scale, o, d_o, lse):
     assert relp.dtype == OP16 and relp.shape[-1] == 2 * rel_width(k_thw)
     drel = torch.empty((B * H, Lq, k_thw[0] + k_thw[1] + k_thw[2]), device=q.device, dtype=F32)
     delta = torch.empty_like(lse)
-    from .ops import workspace
     nbytes = L.call("pvrl_mvit_attn_bwd_workspace_bytes", B, H, Lq, *k_thw)
     ws = workspace(nbytes, q.device, "mvit_attn_bwd")
     L.call("pvrl_mvit_attn_bwd", _ptr(q), _ptr(k), _ptr(v), _ptr(relp), _ptr(keymap(k_thw, q.device)), B, H, Lq, *k_thw,

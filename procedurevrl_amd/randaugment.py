@@ -26,9 +26,13 @@ from collections import namedtuple
 import numpy as np
 import torch
 
+from ._lib import header_constants, struct_dtype
+
 # PVRL_RA_* of include/pvrl.h
-NONE, AFFINE, AUTOCONTRAST, EQUALIZE, INVERT, POSTERIZE, SOLARIZE, SOLARIZE_ADD, COLOR, CONTRAST, BRIGHTNESS, SHARPNESS = range(12)
-BILINEAR, BICUBIC = 2, 3                         # PIL's Image.BILINEAR / Image.BICUBIC
+(NONE, AFFINE, AUTOCONTRAST, EQUALIZE, INVERT, POSTERIZE, SOLARIZE, SOLARIZE_ADD, COLOR, CONTRAST, BRIGHTNESS, SHARPNESS,
+ BILINEAR, BICUBIC) = (header_constants()["PVRL_RA_" + k] for k in (
+    "NONE", "AFFINE", "AUTOCONTRAST", "EQUALIZE", "INVERT", "POSTERIZE", "SOLARIZE", "SOLARIZE_ADD", "COLOR", "CONTRAST", "BRIGHTNESS",
+    "SHARPNESS", "BILINEAR", "BICUBIC"))       # the last two: PIL's Image.BILINEAR / Image.BICUBIC
 NEEDS_STATS = (AUTOCONTRAST, EQUALIZE, CONTRAST)
 GEOMETRIC = ('Rotate', 'ShearX', 'ShearY', 'TranslateXRel', 'TranslateYRel')
 
@@ -224,7 +228,7 @@ def identity_plan(T, width, height, num_layers=2):
     return ClipPlan(None, [[RaOp('none', *_SKIPPED)] * num_layers for _ in range(T)], _FILL, width, height)
 
 
-DESC_DTYPE = np.dtype([("kind", "<i4"), ("resample", "<i4"), ("iarg", "<i4", (2,)), ("c", "<f8", (6,))])   # pvrl_ra_desc
+DESC_DTYPE = struct_dtype("pvrl_ra_desc")
 
 
 class RandAugPlan:

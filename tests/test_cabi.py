@@ -90,3 +90,113 @@ def test_rel_operand_form_round_trips_on_the_host():
             assert float(relp[..., J:JP].float().abs().max()) == 0.0 and float(relp[..., JP + J:].float().abs().max()) == 0.0
             back = om.rel_unpack(relp, k_thw, osc)
             assert float((back - rel).abs().max() / rel.abs().max()) < 2e-5
+
+
+# ---- the header is the one statement of the ABI: struct layouts, enums and limits -------------------------------------
+STRUCT_SIZES = {"pvrl_nt_problem": 104, "pvrl_tn_problem": 96, "pvrl_rows": 40, "pvrl_ln_reduce": 64, "pvrl_cast_problem": 40,
+                "pvrl_mix_desc": 32, "pvrl_ra_desc": 64}       # sizeof on the LP64 hosts the library is built for
+EXPORTED = {"pvrl_nt_problem": "NtProblem", "pvrl_tn_problem": "TnProblem", "pvrl_rows": "Rows", "pvrl_ln_reduce": "LnReduce",
+            "pvrl_cast_problem": "CastProblem"}
+
+
+def _layouts():
+    """-> {struct: (ctypes class, numpy dtype)} for every struct of the header; the five exported classes are the exported objects"""
+    return {name: (getattr(_lib, EXPORTED[name]) if name in EXPORTED else _lib._struct_class(name), _lib.struct_dtype(name))
+            for name in _lib.parse_structs()}
+
+
+def _host_cc():
+    import shutil
+    from procedurevrl_amd.csrc import build_ext
+    hipcc = shutil.which(build_ext._hipcc()) or ""
+    near = [os.path.join(os.path.dirname(os.path.realpath(hipcc)), *rel) for rel in (("clang",), ("..", "llvm", "bin", "clang"),
+                                                                                     ("..", "lib", "llvm", "bin", "clang"))]
+    return shutil.which("cc") or next((c for c in near if hipcc and os.path.exists(c)), None)
+
+
+def test_struct_layouts_match_the_c_compiler(tmp_path):
+    """sizeof and every offsetof, as the host C compiler lays out include/pvrl.h, against the ctypes classes and struct_dtype()"""
+    import subprocess
+    import pytest
+    cc = _host_cc()
+    if cc is None:
+        pytest.skip("no host C compiler")
+    structs = _lib.parse_structs()
+    lines = [f'  printf("{s} - %zu\\n", sizeof({s}));' for s in structs]
+    lines += [f'  printf("{s} {f} %zu\\n", offsetof({s}, {f}));' for s, fields in structs.items() for f, _, _ in fields]
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "pvrl.h"\nint main(void) {\n' + "\n".join(lines) + "\n  return 0;\n}\n")
+    exe = str(tmp_path / "layout")
+    subprocess.run([cc, "-I", os.path.dirname(os.path.abspath(_lib.HEADER)), str(src), "-o", exe], check=True)
+    out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split("\n")
+    seen = 0
+    for s, f, n in (ln.split() for ln in out if ln):
+        cls, dt = _layouts()[s]
+        if f == "-":
+            assert ctypes.sizeof(cls) == int(n) == dt.itemsize, (s, n)
+        else:
+            assert getattr(cls, f).offset == int(n) == dt.fields[f][1], (s, f, n)
+            assert getattr(cls, f).size == dt.fields[f][0].itemsize, (s, f)
+        seen += 1
+    assert seen == len(structs) + sum(len(v) for v in structs.values()) and len(structs) == 7
+
+
+def test_struct_sizes_are_the_pinned_ones():
+    """the same seven sizes as literals: holds on a host without a compiler too"""
+    lay = _layouts()
+    assert sorted(lay) == sorted(STRUCT_SIZES)
+    for name, size in STRUCT_SIZES.items():
+        cls, dt = lay[name]
+        assert ctypes.sizeof(cls) == size == dt.itemsize, name
+        assert [f for f, _ in cls._fields_] == list(dt.names) == [f for f, _, _ in _lib.parse_structs()[name]]
+    assert [f for f, _ in _lib.TnProblem._fields_] == ["P", "ldp", "Q", "ldq", "M", "N", "K", "beta", "dW", "dbias", "gscale", "nonfinite"]
+    assert _lib.struct_dtype("pvrl_ra_desc").fields["c"][0].shape == (6,) and _lib.struct_dtype("pvrl_ra_desc").fields["iarg"][0].shape == (2,)
+
+
+def test_struct_classes_refuse_names_the_header_does_not_have():
+    """a misspelt or dropped field must not become a silent Python attribute next to a null C field"""
+    import pytest
+    c = _lib.CastProblem()
+    setattr(c, "in", 16)
+    c.out, c.out_t, c.R, c.C = 32, None, 3, 5
+    assert getattr(c, "in") == 16 and (c.out, c.out_t, c.R, c.C) == (32, None, 3, 5)
+    for cls in (_lib.CastProblem, _lib.TnProblem, _lib.NtProblem, _lib.LnReduce, _lib.Rows):
+        with pytest.raises(AttributeError):
+            cls().inp = 16
+        with pytest.raises(AttributeError):
+            (cls * 2)()[1].inp = 16
+
+
+def test_limits_come_from_the_header():
+    from procedurevrl_amd import ops, ops_mvit, mvit
+    hc = _lib.header_constants()
+    assert ops.ATTN_MAX_S == 416 == hc["PVRL_ATTN_MAX_S"]
+    assert ops.ATTN_CLS_MAX_S == 4096 == hc["PVRL_ATTN_CLS_MAX_S"]
+    assert ops.TN_GROUP_MAX == 8 == hc["PVRL_TN_GROUP_MAX"]
+    assert (ops.NT_SKINNY_MAX_M, ops.NT_SKINNY_K) == (192, 256) == (hc["PVRL_NT_SKINNY_MAX_M"], hc["PVRL_NT_SKINNY_K"])
+    assert ops.HEAD_DIM == 64 == hc["PVRL_HEAD_DIM"] and ops_mvit.HD == mvit.HD == 96 == hc["PVRL_MVIT_HEAD_DIM"]
+    assert hc is _lib.header_constants()                      # parsed once
+
+
+def test_call_refuses_a_wrong_argument_count():
+    """ctypes alone passes surplus arguments silently; L.call compares with the prototype.  A pure host query: nothing is launched."""
+    import pytest
+    L = _lib.lib()
+    for args in ((768, 768, 8, 1), (768, 768)):
+        with pytest.raises(_lib.PvrlError, match=rf"pvrl_gemm_tn_workspace_bytes takes 3 arguments .* {len(args)} given"):
+            L.call("pvrl_gemm_tn_workspace_bytes", *args)
+
+
+def test_struct_parser_refuses_what_it_does_not_understand():
+    import pytest
+    ok = "typedef struct s {\n  const float* a; int64_t m, n;\n  double c[6];\n} s;"
+    assert _lib.parse_structs(ok) == {"s": [("a", "const float*", None), ("m", "int64_t", None), ("n", "int64_t", None), ("c", "double", 6)]}
+    for body in ("int a : 3;",                                  # bit-field
+                 "struct { int a; } inner;",                    # nested struct
+                 "int (*fn)(int);",                             # function pointer
+                 "unsigned int a;", "size_t a;", "pvrl_rows r;", "int a[N];", "float *a, *b;"):
+        with pytest.raises(_lib.PvrlError):
+            _lib.parse_structs("typedef struct s { int64_t n; %s } s;" % body)
+    for txt in ("typedef struct { int a; } s;", "typedef struct t { int a; } s;", "struct s { int a; };"):
+        with pytest.raises(_lib.PvrlError):
+            _lib.parse_structs(txt)

@@ -131,6 +131,19 @@ def test_descriptors_carry_the_plan():
     assert (d[:, 6].view(np.float32) == plan.lam).all() and (d[:, 7].view(np.float32) == plan.lam_partner).all()
 
 
+def test_descriptor_bytes_are_the_header_layout():
+    """the layout contract once more, outside the code under test: `pvrl_mix_desc` is {int32 partner, kind, t0, t1, h0, h1; float lam,
+    lam_partner} and the kinds are the PVRL_MIX_* numbers of include/pvrl.h, written out here as literals"""
+    import struct
+    plan = mx.MixPlan("elem", np.array([3, 2, 1, 0], np.int32), np.array([mx.CUT, mx.BLEND, mx.NONE, mx.CUT], np.int32),
+                      np.array([[1, 9, 2, 7], [0, 0, 0, 0], [0, 0, 0, 0], [4, 5, 0, 16]], np.int32),
+                      np.array([0.75, 0.3, 1.0, 0.984375], np.float32), np.array([0.25, 0.7, 0.0, 0.015625], np.float32), 0.91, 0.01)
+    want = (struct.pack("<6i2f", 3, 2, 1, 9, 2, 7, 0.75, 0.25) + struct.pack("<6i2f", 2, 1, 0, 0, 0, 0, 0.3, 0.7)
+            + struct.pack("<6i2f", 1, 0, 0, 0, 0, 0, 1.0, 0.0) + struct.pack("<6i2f", 0, 2, 4, 5, 0, 16, 0.984375, 0.015625))
+    d = plan.descriptors()
+    assert d.dtype == np.int32 and d.shape == (4, 8) and d.tobytes() == want and len(want) == 4 * 32
+
+
 def test_finetune_loss_under_mixup_needs_the_plan_and_num_seg_is_refused():
     from procedurevrl_amd import train_net as tn
     from procedurevrl_amd.config import get_cfg

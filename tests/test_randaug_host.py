@@ -144,6 +144,22 @@ def test_descriptors_match_the_header_layout():
         ra.RandAugPlan([clips[0], ra.clip_plan(3, 2, 50, 37)])
 
 
+def test_descriptor_bytes_are_the_header_layout():
+    """the layout contract once more, outside the code under test: `pvrl_ra_desc` is {int32 kind, resample, iarg[2]; double c[6]} and
+    the kinds are the PVRL_RA_* numbers of include/pvrl.h, written out here as literals.  [layers][frames], layer-major."""
+    import struct
+    op = lambda kind, args, resample=None: ra.RaOp("x", True, (), resample, kind, args)
+    frames = [[op(ra.AFFINE, (1.0, 0.25, -3.5, 0.0, 1.0, 2.0), ra.BICUBIC), op(ra.POSTERIZE, (4,))],
+              [op(ra.SOLARIZE_ADD, (110, 128)), op(ra.COLOR, (1.75,))]]
+    d = ra.RandAugPlan([ra.ClipPlan(0, frames, (128, 128, 128), 50, 37)]).descriptors()
+    assert d.shape == (2, 2) and d.dtype == ra.DESC_DTYPE
+    want = (struct.pack("<ii2i6d", 1, 3, 0, 0, 1.0, 0.25, -3.5, 0.0, 1.0, 2.0)         # layer 0: frame 0 AFFINE / BICUBIC
+            + struct.pack("<ii2i6d", 7, 0, 110, 128, 0, 0, 0, 0, 0, 0)                 #          frame 1 SOLARIZE_ADD
+            + struct.pack("<ii2i6d", 5, 0, 4, 0, 0, 0, 0, 0, 0, 0)                     # layer 1: frame 0 POSTERIZE
+            + struct.pack("<ii2i6d", 8, 0, 0, 0, 1.75, 0, 0, 0, 0, 0))                 #          frame 1 COLOR
+    assert d.tobytes() == want and len(want) == 4 * 64
+
+
 def test_decoded_train_batch_without_randaugment_draws_as_before():
     cfg = get_cfg()
     assert cfg.DATA.USE_RAND_AUGMENT is False
