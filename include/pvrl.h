@@ -43,6 +43,8 @@ extern "C" {
 #define PVRL_EPI_RESID_16 7  /* out0 bf16 = aux + rowscale * (acc + bias) + bias2: the residual add on the 16-bit patch rows of the
                               * split residual stream (pvrl_rows); aux bf16 [M, aux_ld], or -- aux_rowmod != 0 -- the fp32 table
                               * aux_f32[m % rowmod] of the embedding prologue (vit.py:370-407)            */
+#define PVRL_EPI_GELU_ONLY 8 /* out0 bf16 = GELU_erf(acc + bias), no out1: PVRL_EPI_GELU's out1, the same 16 bits, for a forward
+                              * that keeps no pre-activation (eval; the first pass over a checkpointed block) */
 
 /* The 16-bit operand type this library was built with: 0 = bf16 (libpvrl_hip.so), 1 = fp16 (libpvrl_hip_f16.so, built
  * with -DPVRL_OPERAND_F16).  Wherever an entry point below says "bf16" (names, PVRL_EPI_BF16, comments) read "the

@@ -123,7 +123,9 @@ constexpr int NT_MID_M = 2048;
 //  launch serialises behind the first; one launch with a partly idle last wave wins.)
 template <int EPI>
 int launch_nt(const GemmNT& p, hipStream_t s) {
-  constexpr bool two_out = EPI == PVRL_EPI_GELU || EPI == PVRL_EPI_QGELU;
+  // (PVRL_EPI_GELU_ONLY takes PVRL_EPI_GELU's tile at every shape: the same kernel family sums k in the same order, so its one output
+  //  is PVRL_EPI_GELU's second bit for bit)
+  constexpr bool act_out = EPI == PVRL_EPI_GELU || EPI == PVRL_EPI_QGELU || EPI == PVRL_EPI_GELU_ONLY;
   if (nt_skinny_ok(p)) return launch_nt_skinny<EPI>(p, s);
   if (p.N == 768 && p.M >= 4096 && p.M < 20000) return launch_tile<EPI, 2, 6>(p, s);   // MViT stage 4 (M = 12,576): 99 tiles of 128 x 384 x 2 fill 198 CUs; 256 x 256 tiles 150 (-10 %)
   if (p.M >= 4096 && p.N % 256 == 0) {
@@ -139,7 +141,7 @@ int launch_nt(const GemmNT& p, hipStream_t s) {
     if (p.N % 384 == 0 && p.M >= 100000) return launch_tile<EPI, 2, 6>(p, s);
     if (p.N % 320 == 0) return launch_tile<EPI, 2, 5>(p, s);
   }
-  if (p.M >= NT_MID_M && (p.N % 256 == 0 || two_out)) return launch_tile<EPI, 4, 2>(p, s);
+  if (p.M >= NT_MID_M && (p.N % 256 == 0 || act_out)) return launch_tile<EPI, 4, 2>(p, s);
   return launch_tile<EPI, 2, 2>(p, s);
 }
 
@@ -173,6 +175,7 @@ extern "C" int pvrl_gemm_nt_bf16(const void* A, int64_t lda, const void* W, int6
     case PVRL_EPI_DGELU: return launch_nt<PVRL_EPI_DGELU>(p, s);
     case PVRL_EPI_DQGELU: return launch_nt<PVRL_EPI_DQGELU>(p, s);
     case PVRL_EPI_RESID_16: return launch_nt<PVRL_EPI_RESID_16>(p, s);
+    case PVRL_EPI_GELU_ONLY: return launch_nt<PVRL_EPI_GELU_ONLY>(p, s);
     default: return PVRL_EINVAL;
   }
 }

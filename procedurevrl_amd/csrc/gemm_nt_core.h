@@ -239,6 +239,16 @@ __device__ __forceinline__ void nt_epilogue_at(const GemmNT& p, f32x4 (&acc)[4][
 #pragma unroll
             for (int e = 0; e < 8; ++e) o0[e] = (op_t)(rs * v[e]);
             bst16(r0, o0off, o0);
+          } else if constexpr (EPI == PVRL_EPI_GELU_ONLY) {
+            // PVRL_EPI_GELU's g from the same fp32 v, without its u: one store per lane and column group
+            opx8 g0;
+#pragma unroll
+            for (int e = 0; e < 8; e += 2) {
+              const f32x2_t gg = gelu_erf2((f32x2_t){v[e], v[e + 1]});
+              g0[e] = (op_t)gg[0];
+              g0[e + 1] = (op_t)gg[1];
+            }
+            bst16(r0, o0off, g0);
           } else if constexpr (TWO) {
             opx8 u0, g0;
 #pragma unroll

@@ -76,6 +76,9 @@ __global__ __launch_bounds__(64 * SK_NW) void gemm_nt_skinny_kernel(GemmNT p) {
       reinterpret_cast<float*>(p.out0)[(long)m * p.ld0 + n] = rs * (s + b);
     } else if constexpr (EPI == PVRL_EPI_BF16) {
       reinterpret_cast<op_t*>(p.out0)[(long)m * p.ld0 + n] = (op_t)(rs * (s + b));
+    } else if constexpr (EPI == PVRL_EPI_GELU_ONLY) {
+      const float u = s + b;
+      reinterpret_cast<op_t*>(p.out0)[(long)m * p.ld0 + n] = (op_t)gelu_erf2((f32x2_t){u, u})[0];
     } else if constexpr (EPI == PVRL_EPI_GELU || EPI == PVRL_EPI_QGELU) {
       const float u = s + b;
       reinterpret_cast<op_t*>(p.out0)[(long)m * p.ld0 + n] = (op_t)u;

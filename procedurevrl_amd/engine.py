@@ -61,6 +61,25 @@ class _X:
         return self.p if self.full is not None else ops.SplitRows(self.p, None)
 
 
+def storage_nbytes(obj, seen=None):
+    """bytes of the distinct storages under `obj` (tensors, `_X` stages, dicts, lists, tuples); views of one storage -- and a tensor two
+    entries share, like the cls rows `x1.c is x0.c` of the split stream -- count once.  `seen`: storages already counted elsewhere."""
+    seen = set() if seen is None else seen
+    if isinstance(obj, torch.Tensor):
+        st = obj.untyped_storage()
+        if st.data_ptr() in seen:
+            return 0
+        seen.add(st.data_ptr())
+        return st.nbytes()
+    if isinstance(obj, _X):
+        obj = (obj.p, obj.c, obj.full)
+    elif isinstance(obj, dict):
+        obj = obj.values()
+    elif not isinstance(obj, (list, tuple)):
+        return 0
+    return sum(storage_nbytes(v, seen) for v in obj)
+
+
 class EncoderEngine(GraphReplay):
     def __init__(self, model):
         """`model` is a procedurevrl_amd.vit.VisionTransformer (same parameter names as the reference)."""
@@ -111,6 +130,11 @@ class EncoderEngine(GraphReplay):
         # correct only while nothing reads them.  PVRL_DEBUG_NAN_UNDEFINED=1 fills every such region with NaN, so a reader that should
         # not exist turns the loss / gradients NaN (tests/e2e_checks.check_train_step_undefined_rows_nan_filled runs the suite's steps so).
         self.debug_nan_undefined = os.environ.get("PVRL_DEBUG_NAN_UNDEFINED", "0") == "1"
+        # MODEL.ACT_CHECKPOINT (the reference's defaults.py:413): a training forward keeps, of every block but the last, its input stage
+        # and its DropPath scales alone; the backward runs that block's forward again (_recompute) in front of its own kernels.  No
+        # training kernel uses atomics, so the recomputed activations -- hence features and gradients -- are the plain path's bit for
+        # bit.  The last block is kept whole: its activations are the first the backward frees, the peak would be the same.
+        self.act_checkpoint = bool(model.cfg.MODEL.ACT_CHECKPOINT)
         self._wq = []
         self._keep = None
         self._graph_init()            # HIP-graph replay of the step (GraphReplay)
@@ -392,7 +416,7 @@ class EncoderEngine(GraphReplay):
         M = R + B
         C = self.C
         dev = frames.device
-        sv = dict(B=B, T=T, N=N, R=R, M=M, Wp=Wp, blocks=[])
+        sv = dict(B=B, T=T, N=N, R=R, M=M, Wp=Wp, blocks=[], ckpt=bool(save and self.act_checkpoint))
 
         if isinstance(frames, DecodedClips):     # decoded uint8 clips: GPU-side normalise/rescale/crop/flip + im2col
             a_pe = ops.frames_u8_patchify(frames)
@@ -410,10 +434,12 @@ class EncoderEngine(GraphReplay):
         if droppath is None:
             droppath = (self._droppath_undivided if self.undivided else self._droppath_all)(B, N, T, dev, training)
         for i, blk in enumerate(m.blocks):
+            last = i == len(m.blocks) - 1
+            ckpt = save and self.act_checkpoint and not last
             if self.undivided:
-                x = self._block_fwd_undivided(blk, x, sv, droppath[i], save)
+                x = self._block_fwd_undivided(blk, x, sv, droppath[i], save, ckpt=ckpt)
             else:
-                x = self._block_fwd(blk, x, sv, droppath[i], save, last=i == len(m.blocks) - 1)
+                x = self._block_fwd(blk, x, sv, droppath[i], save, last=last, ckpt=ckpt)
 
         if frames_per_clip:         # vit.py:414-416: the mean over the frames, in front of the final norm (only x[:, 0] is read)
             sv["frames_per_clip"] = frames_per_clip
@@ -432,6 +458,10 @@ class EncoderEngine(GraphReplay):
                 gs = self.grad_store()
                 lib().call("pvrl_nonfinite_flag_f32", ops._ptr(feat), feat.numel(), ops._ptr(gs.bad), ops._stream())
         return feat
+
+    def saved_nbytes(self):
+        """bytes the last training forward keeps for its backward: the distinct storages under `self.saved` (storage_nbytes)"""
+        return storage_nbytes(self.saved)
 
     def stream_from_rows(self, x_rows, B):
         """fp32 [B*N*T + B, C] (patch rows, then cls rows) -> a stage of the residual stream as this engine keeps it (tests / probes)"""
@@ -462,16 +492,29 @@ class EncoderEngine(GraphReplay):
         gc = ops.cls_linear(hc, P(blk.mlp.fc1.weight), P(blk.mlp.fc1.bias), gelu=True)
         ops.cls_linear(gc, P(blk.mlp.fc2.weight), P(blk.mlp.fc2.bias), rowscale=s3c, biasscale=s3c, aux=xc, out=out)
 
-    def _mlp_fwd(self, blk, x, s3_all, sv, whole=False):
+    def _fc1(self, blk, h_m, keep_u):
+        """-> (u, g) = (fc1(h_m), GELU(u)) in the 16-bit operand type; u is None unless `keep_u` (only the backward's PVRL_EPI_DGELU reads
+        it: without it the GEMM's largest output of the block is not written)"""
+        L = lib()
+        w1, b1 = self._weight(blk.mlp.fc1.weight).w, blk.mlp.fc1.bias.detach()
+        if keep_u:
+            return ops.gemm_nt(h_m, w1, L.PVRL_EPI_GELU, bias=b1)
+        return None, ops.gemm_nt(h_m, w1, L.PVRL_EPI_GELU_ONLY, bias=b1)
+
+    def _mlp_fwd(self, blk, x, s3_all, sv, whole=False, keep_u=True, recompute=False):
         """x + s3 * mlp(norm2(x)) on every row (vit.py:155-157) -> (the next stage, h_m, (mean_m, rstd_m), u, g): what the block saves.
-        `whole`: the one-buffer fp32 stream of the divided path, fc2 as ONE GEMM over all rows"""
+        `whole`: the one-buffer fp32 stream of the divided path, fc2 as ONE GEMM over all rows.  `keep_u` False: nobody will read the
+        pre-activation u (it is None; PVRL_EPI_GELU_ONLY writes the same g).  `recompute`: a checkpointed block's second pass -- the
+        next stage exists already, so fc2, the cls rows' fp32 chain and the stage's allocation are skipped (it is None)"""
         L = lib()
         B, R = sv["B"], sv["R"]
         P = lambda t: t.detach()
+        h_m, mean_m, rstd_m = ops.layernorm_fwd(x.all(), P(blk.norm2.weight), P(blk.norm2.bias), self.eps)
+        u, g = self._fc1(blk, h_m, keep_u)
+        if recompute:
+            return None, h_m, (mean_m, rstd_m), u, g
         y = _X.new(R, B, self.C, x.c.device, sv["split"])
         s3c = s3_all[R:] if s3_all is not None else None
-        h_m, mean_m, rstd_m = ops.layernorm_fwd(x.all(), P(blk.norm2.weight), P(blk.norm2.bias), self.eps)
-        u, g = ops.gemm_nt(h_m, self._weight(blk.mlp.fc1.weight).w, L.PVRL_EPI_GELU, bias=P(blk.mlp.fc1.bias))
         w2 = self._weight(blk.mlp.fc2.weight).w
         if whole:
             ops.gemm_nt(g, w2, L.PVRL_EPI_RESID_F32, bias=P(blk.mlp.fc2.bias), rowscale=s3_all, aux=x.full, out0=y.full)
@@ -492,9 +535,12 @@ class EncoderEngine(GraphReplay):
         self._lin_wgrad(gs, du, s["h_m"], blk.mlp.fc1)
         return ops.gemm_nt(du, self._weight(blk.mlp.fc1.weight).t, L.PVRL_EPI_BF16)
 
-    def _block_fwd(self, blk, x0, sv, dp, save, last=False):
-        """`last`: the encoder's last block (with prune_last: the patch rows of x2 / x3 are neither computed nor defined)"""
+    def _block_fwd(self, blk, x0, sv, dp, save, last=False, ckpt=False, recompute=False):
+        """`last`: the encoder's last block (with prune_last: the patch rows of x2 / x3 are neither computed nor defined).
+        `ckpt` (act_checkpoint, never the last block): the entry saved is x0 and dp alone.  `recompute`: the backward's second pass over
+        such a block from that entry -- the full entry again, without the next stage (_mlp_fwd) -> None"""
         prune = last and self.prune_last
+        keep_u = save and not ckpt
         L = lib()
         B, T, N, R, M = sv["B"], sv["T"], sv["N"], sv["R"], sv["M"]
         C, H = self.C, self.H
@@ -569,15 +615,17 @@ class EncoderEngine(GraphReplay):
             h_m = mean_m = rstd_m = u = g = None
             if save or not self.cls_fp32:
                 h_m, mean_m, rstd_m = ops.layernorm_fwd(x2.c, P(blk.norm2.weight), P(blk.norm2.bias), self.eps)
-                u, g = ops.gemm_nt(h_m, self._weight(blk.mlp.fc1.weight).w, L.PVRL_EPI_GELU, bias=P(blk.mlp.fc1.bias))
+                u, g = self._fc1(blk, h_m, keep_u)
             if self.cls_fp32:
                 self._cls_mlp_fp32(blk, x2.c, s3c, x3.c)
             else:
                 ops.gemm_nt(g, self._weight(blk.mlp.fc2.weight).w, L.PVRL_EPI_RESID_F32, bias=P(blk.mlp.fc2.bias), rowscale=s3c,
                             aux=x2.c, out0=x3.c)
         else:
-            x3, h_m, (mean_m, rstd_m), u, g = self._mlp_fwd(blk, x2, s3_all, sv, whole=not split)
-        if save:
+            x3, h_m, (mean_m, rstd_m), u, g = self._mlp_fwd(blk, x2, s3_all, sv, whole=not split, keep_u=keep_u, recompute=recompute)
+        if ckpt:
+            sv["blocks"].append(dict(ckpt=True, x0=x0, dp=dp))
+        elif save:
             sv["blocks"].append(dict(x0=x0, x1=x1, x2=x2, h_t=h_t, st_t=(mean_t, rstd_t), qkv_t=qkv_t, o_t=o_t,
                                      lse_t=lse_t, h_s=h_s, st_s=(mean_s, rstd_s), qkv_s=qkv_s, o_s=o_s,
                                      lse_s=lse_s, h_m=h_m, st_m=(mean_m, rstd_m), u=u, g=g, dp=dp, pruned=prune, cls_attn=cls_attn))
@@ -590,9 +638,9 @@ class EncoderEngine(GraphReplay):
         streamed ones (ops.attn_family, the one dispatch rule of every scheme)."""
         return ops.attn_seq_fwd(qkv, B, S, self.H, self.scale, mode=1, T=1, cls_base=R, o=o[:R], o_cls=o[R:])[2]
 
-    def _block_fwd_undivided(self, blk, x0, sv, dp, save):
+    def _block_fwd_undivided(self, blk, x0, sv, dp, save, ckpt=False, recompute=False):
         """x += dp * proj(attn(norm1(x))); x += dp * mlp(norm2(x))   (Block.forward, vit.py:124-127) on the rows of `_X`.  No pruning of
-        the last block; the cls rows' projection and MLP run in fp32 (cls_fp32) as in the divided path."""
+        the last block; the cls rows' projection and MLP run in fp32 (cls_fp32) as in the divided path.  `ckpt` / `recompute`: _block_fwd"""
         L = lib()
         B, T, N, R, M = sv["B"], sv["T"], sv["N"], sv["R"], sv["M"]
         C = self.C
@@ -617,8 +665,10 @@ class EncoderEngine(GraphReplay):
             ops.gemm_nt(o_s[R:], wproj, L.PVRL_EPI_RESID_F32, bias=P(blk.attn.proj.bias), rowscale=row(s2_all, R, M), aux=x0.c, out0=x1.c)
 
         # ---- MLP ----
-        x2, h_m, st_m, u, g = self._mlp_fwd(blk, x1, dp["s3_all"] if dp else None, sv)
-        if save:
+        x2, h_m, st_m, u, g = self._mlp_fwd(blk, x1, dp["s3_all"] if dp else None, sv, keep_u=save and not ckpt, recompute=recompute)
+        if ckpt:
+            sv["blocks"].append(dict(ckpt=True, x0=x0, dp=dp))
+        elif save:
             sv["blocks"].append(dict(undivided=True, x0=x0, x1=x1, h_s=h_s, st_s=(mean_s, rstd_s), qkv_s=qkv_s, o_s=o_s, lse_s=lse_s,
                                      h_m=h_m, st_m=st_m, u=u, g=g, dp=dp))
         return x2
@@ -670,7 +720,7 @@ class EncoderEngine(GraphReplay):
     def _graph_key(self, frames, training, save):
         m = self.m
         # parameter / gradient storage is baked into a graph: a re-homed parameter (optimizer flat buffer, .to()) is a new key
-        return (tuple(frames.shape), frames.dtype, bool(training), bool(save), frames.device.index, tuple(m.drop_path_rates),
+        return (tuple(frames.shape), frames.dtype, bool(training), bool(save), bool(self.act_checkpoint), frames.device.index, tuple(m.drop_path_rates),
                 m.blocks[0].attn.qkv.weight.data_ptr(), m.norm.weight.data_ptr(), self.grad_store().flat.data_ptr())
 
     def _graph_reset_host_state(self):
@@ -752,11 +802,31 @@ class EncoderEngine(GraphReplay):
             dy = ops.cast_scale(dx.full, s3)
         return dict(sv=sv, gs=gs, dx=dx, dy=dy, dxp_zero=dxp_zero)
 
+    def _recompute(self, blk, s, sv):
+        """a checkpointed block's entry (x0, dp) -> the entry a plain forward would have saved: the block's forward once more (the same
+        launches on the same operands -- the weight copies and the fused temporal map W_e are the forward's, _weight / _fused_temporal
+        -- less what no backward reads, _mlp_fwd).  Inside _bwd_block: stage boundaries and the hook order are the plain backward's."""
+        one = dict(sv, blocks=[])
+        fwd = self._block_fwd_undivided if self.undivided else self._block_fwd
+        fwd(blk, s["x0"], one, s["dp"], True, recompute=True)
+        return one["blocks"][0]
+
     def _bwd_block(self, st, i):
         sv = st["sv"]
         nxt = sv["blocks"][i - 1]["dp"] if i > 0 else None
-        st["dy"] = self._block_bwd(self.m.blocks[i], sv["blocks"][i], sv, st["dx"], st["gs"], st["dy"], i > 0, nxt,
+        s = sv["blocks"][i]
+        if s.get("ckpt"):
+            s = self._recompute(self.m.blocks[i], s, sv)
+        st["dy"] = self._block_bwd(self.m.blocks[i], s, sv, st["dx"], st["gs"], st["dy"], i > 0, nxt,
                                    dxp_zero=st.get("dxp_zero", False))
+        del s
+        if sv["ckpt"]:
+            # What the blocks defer to the end of the backward -- a LayerNorm partial-sum workspace per norm (sized by the grid: 1.8 MB
+            # at 784 rows, 4.7 MB at 50k), dW_e / db_e per block -- grows while the saved stages go.  With few rows per step it outweighs
+            # them and moves the peak to block 0 (2 clips of 2 x 224^2, depth 4: 82.8 MB instead of 69.0).  This mode pays time for
+            # memory: finish the deferred work per block -- the same per-item arithmetic; at the headline shape neither the peak (it is
+            # at the first recomputed block) nor the step time moves measurably.
+            self._finish_deferred(st["gs"])
         st["dxp_zero"] = False
         sv["blocks"][i] = None  # free activations as we go
 

@@ -107,6 +107,8 @@ def _check_cfg(cfg):
     if float(mv.LAYER_SCALE_INIT_VALUE) != 0.0: bad.append("LAYER_SCALE_INIT_VALUE > 0")
     if mv.NORM_STEM or mv.USE_MEAN_POOLING or mv.PATCH_2D or mv.NORM != "layernorm": bad.append("NORM_STEM/USE_MEAN_POOLING/PATCH_2D/NORM")
     if not mv.QKV_BIAS: bad.append("QKV_BIAS False")
+    # the TimeSformer engine recomputes checkpointed blocks bit for bit; this engine's backward has accumulating kernels and no recompute
+    if cfg.MODEL.ACT_CHECKPOINT: bad.append("MODEL.ACT_CHECKPOINT True")
     if bad:
         raise NotImplementedError("MViT on the HIP path is built for the shipped MViTv2-S configuration "
                                   "(configs/HowTo100M/procedurevrl_mvitv2_*.yaml); unsupported here: " + ", ".join(bad))

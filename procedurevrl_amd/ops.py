@@ -18,7 +18,7 @@ F32 = torch.float32
 
 # When set to a list, gemm launches are bracketed with events on the launch stream (bench.py roofline leg).
 KERNEL_TIMING = None
-_EPI_NAMES = {0: "op16", 1: "gelu", 2: "qgelu", 3: "resid_f32", 4: "f32", 5: "dgelu", 6: "dqgelu", 7: "resid_16"}
+_EPI_NAMES = {0: "op16", 1: "gelu", 2: "qgelu", 3: "resid_f32", 4: "f32", 5: "dgelu", 6: "dqgelu", 7: "resid_16", 8: "gelu_only"}
 
 
 def _timed(name, flops, fn):
@@ -95,7 +95,7 @@ def _ptr_ld(t):
 # GEMMs
 # ----------------------------------------------------------------------------------------
 def gemm_nt(A, W, epi, bias=None, rowscale=None, aux=None, aux_rowmod=0, out0=None, out1=None, bias2=None):
-    """epilogue(A[M,K] @ W[N,K]^T).  Returns out0 (and out1 for the GELU epilogues)."""
+    """epilogue(A[M,K] @ W[N,K]^T).  Returns out0 (and out1 for the two-output GELU epilogues; PVRL_EPI_GELU_ONLY has out0 = g alone)."""
     L = lib()
     _chk2d(A, OP16); _chk2d(W, OP16)
     M, K = A.shape
