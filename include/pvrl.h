@@ -313,7 +313,8 @@ int pvrl_milnce(const float* x, int64_t n, int64_t C, float grad_scale, float* n
  * the update (1 - lr*wd, 1 - beta, lr / bias_correction1 ...) are formed in double and rounded once, like torch's.
  * `skip` (device pointer or null): when *skip != 0 the call leaves p and the state untouched -- the device-side form of
  * `misc.check_nan_losses(loss)` raising in front of optimizer.step() (tools/train_net.py:174): the flag is the non-finiteness of
- * the loss (and, for the fp16 flavour, of the gradients: pvrl_nonfinite_flag_f32), no host sync per iteration. */
+ * the loss (and, for the fp16 flavour, of the gradients: pvrl_nonfinite_flag_f32), no host sync per iteration.
+ * pvrl_adam_step: p, g, m and v must be 16-byte aligned (PVRL_EINVAL otherwise, before any launch); pvrl_sgd_step takes any fp32 pointer. */
 int pvrl_adam_step(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
                    double eps, double weight_decay, int64_t step, double gscale, int decoupled, const float* skip, void* stream);
 int pvrl_sgd_step(float* p, const float* g, float* buf, int64_t n, double lr, double momentum, double dampening,

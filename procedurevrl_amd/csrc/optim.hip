@@ -164,6 +164,7 @@ extern "C" int pvrl_adam_step(float* p, const float* g, float* m, float* v, int6
                               const float* skip, void* stream) {
   if (n <= 0) return PVRL_OK;
   if (!p || !g || !m || !v || step < 1) return PVRL_EINVAL;
+  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return PVRL_EINVAL;   // adam_kernel takes f32x4 loads
   const double bc1 = 1.0 - pow(beta1, (double)step);
   const double bc2 = 1.0 - pow(beta2, (double)step);
   AdamConst c;

@@ -12,7 +12,10 @@ import torch
 TOL = 1e-6
 
 
-def _run(method):
+NESTEROV, DAMPENED = (0.9, 0.0, True), (0.9, 0.1, False)         # SGD (momentum, dampening, nesterov)
+
+
+def _run(method, sgd=NESTEROV):
     import e2e_checks as ec
     from procedurevrl_amd.datasets import synthetic_label_emb
     from procedurevrl_amd.optimizer import construct_optimizer, set_lr
@@ -22,7 +25,7 @@ def _run(method):
     cfg.SOLVER.WEIGHT_DECAY = 1e-2
     cfg.BN.WEIGHT_DECAY = 3e-3
     cfg.TRAIN.MULT = 0.1                       # fine-tuning grouping: encoder (lr_mult 0.1) / head + order transformer
-    cfg.SOLVER.MOMENTUM, cfg.SOLVER.DAMPENING, cfg.SOLVER.NESTEROV = 0.9, 0.0, True
+    cfg.SOLVER.MOMENTUM, cfg.SOLVER.DAMPENING, cfg.SOLVER.NESTEROV = sgd
     model = ec.build(cfg, synthetic_label_emb(64, 512, seed=1))
     with torch.no_grad():
         for p in model.parameters():           # no parameter sits at exactly zero
@@ -96,9 +99,10 @@ def _run(method):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("method", ["adamw", "adam", "sgd"])
-def test_fused_step_matches_torch_optim(method):
-    worst = _run(method)
+@pytest.mark.parametrize("method,sgd", [("adamw", NESTEROV), ("adam", NESTEROV), ("sgd", NESTEROV), ("sgd", DAMPENED)],
+                         ids=["adamw", "adam", "sgd", "sgd-dampening0.1-no_nesterov"])
+def test_fused_step_matches_torch_optim(method, sgd):
+    worst = _run(method, sgd)
     print(method, worst)
     for k, v in worst.items():
         assert v <= TOL, (method, k, v, worst)
