@@ -1,5 +1,6 @@
 // bf16 MFMA GEMM, "NT" form: the C-ABI entry points.  The kernel, its epilogues and the tile launcher live in
 // gemm_nt_core.h (shared with the measured-and-rejected variants kept under tools/probe/, which are NOT part of this library).
+#include <type_traits>
 #include "gemm_nt_core.h"
 #include "gemm_nt8_core.h"
 #include "gemm_nt_skinny.h"
@@ -145,6 +146,27 @@ int launch_nt(const GemmNT& p, hipStream_t s) {
   return launch_tile<EPI, 2, 2>(p, s);
 }
 
+// One problem's kernel argument: the fields every entry has (q) and those only pvrl_gemm_nt_bf16 has; tiles_m / tiles_n / nwg and,
+// where gm stays 0, the rasterisation group height are the launcher's
+GemmNT nt_problem(const pvrl_nt_problem& q, const float* bias2, int64_t aux_rowmod, void* out1, int64_t ld1, int tails) {
+  GemmNT p = {};
+  p.A = (const op_t*)q.A; p.lda = q.lda; p.W = (const op_t*)q.W; p.ldw = q.ldw;
+  p.M = (int)q.M; p.N = (int)q.N; p.K = (int)q.K;
+  p.bias = q.bias; p.bias2 = bias2; p.rowscale = q.rowscale; p.aux = q.aux; p.aux_ld = q.aux_ld; p.aux_rowmod = (int)aux_rowmod;
+  p.out0 = q.out0; p.ld0 = q.ld0; p.out1 = out1; p.ld1 = ld1;
+  p.cus = pvrl_compute_cus_per_xcd(); p.tails = tails;
+  return p;
+}
+
+// run-time epilogue -> template argument, over the epilogues E, REST... that an entry point takes: f(std::integral_constant<int, EPI>);
+// PVRL_EINVAL for any other
+template <int E, int... REST, typename F>
+int with_epilogue(int epilogue, F&& f) {
+  if (epilogue == E) return f(std::integral_constant<int, E>{});
+  if constexpr (sizeof...(REST) > 0) return with_epilogue<REST...>(epilogue, f);
+  else return PVRL_EINVAL;
+}
+
 }  // namespace
 
 extern "C" int pvrl_gemm_nt_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, int64_t M, int64_t N,
@@ -159,25 +181,10 @@ extern "C" int pvrl_gemm_nt_bf16(const void* A, int64_t lda, const void* W, int6
   if ((epilogue == PVRL_EPI_RESID_F32 || epilogue == PVRL_EPI_RESID_16 || epilogue == PVRL_EPI_DGELU || epilogue == PVRL_EPI_DQGELU) &&
       (!aux || (aux_ld % 8)))
     return PVRL_EINVAL;
-  GemmNT p;
-  p.A = (const op_t*)A; p.lda = lda; p.W = (const op_t*)W; p.ldw = ldw;
-  p.M = (int)M; p.N = (int)N; p.K = (int)K;
-  p.bias = bias; p.bias2 = bias2; p.rowscale = rowscale; p.aux = aux; p.aux_ld = aux_ld; p.aux_rowmod = (int)aux_rowmod;
-  p.out0 = out0; p.ld0 = ld0; p.out1 = out1; p.ld1 = ld1; p.m_off = 0; p.gm = 0;      // 0: launch_tile picks the rasterisation group height for the shape
-  p.cus = pvrl_compute_cus_per_xcd(); p.tails = 1;
-  hipStream_t s = (hipStream_t)stream;
-  switch (epilogue) {
-    case PVRL_EPI_BF16: return launch_nt<PVRL_EPI_BF16>(p, s);
-    case PVRL_EPI_GELU: return launch_nt<PVRL_EPI_GELU>(p, s);
-    case PVRL_EPI_QGELU: return launch_nt<PVRL_EPI_QGELU>(p, s);
-    case PVRL_EPI_RESID_F32: return launch_nt<PVRL_EPI_RESID_F32>(p, s);
-    case PVRL_EPI_F32: return launch_nt<PVRL_EPI_F32>(p, s);
-    case PVRL_EPI_DGELU: return launch_nt<PVRL_EPI_DGELU>(p, s);
-    case PVRL_EPI_DQGELU: return launch_nt<PVRL_EPI_DQGELU>(p, s);
-    case PVRL_EPI_RESID_16: return launch_nt<PVRL_EPI_RESID_16>(p, s);
-    case PVRL_EPI_GELU_ONLY: return launch_nt<PVRL_EPI_GELU_ONLY>(p, s);
-    default: return PVRL_EINVAL;
-  }
+  const GemmNT p = nt_problem({A, lda, W, ldw, M, N, K, bias, rowscale, aux, aux_ld, out0, ld0}, bias2, aux_rowmod, out1, ld1, 1);
+  return with_epilogue<PVRL_EPI_BF16, PVRL_EPI_GELU, PVRL_EPI_QGELU, PVRL_EPI_RESID_F32, PVRL_EPI_F32, PVRL_EPI_DGELU, PVRL_EPI_DQGELU,
+                       PVRL_EPI_RESID_16, PVRL_EPI_GELU_ONLY>(
+      epilogue, [&](auto e) { return launch_nt<decltype(e)::value>(p, (hipStream_t)stream); });
 }
 
 extern "C" int pvrl_gemm_nt_batched_bf16(int nprob, const pvrl_nt_problem* problems, int epilogue, void* stream) {
@@ -192,23 +199,17 @@ extern "C" int pvrl_gemm_nt_batched_bf16(int nprob, const pvrl_nt_problem* probl
       const pvrl_nt_problem& q = problems[i0 + i];
       if (!q.A || !q.W || !q.out0 || q.M <= 0 || q.N <= 0 || q.K <= 0 || (q.N % 128) || (q.K % BK)) return PVRL_EINVAL;
       if ((q.lda % 8) || (q.ldw % 8) || (q.ld0 % 8) || (epilogue == PVRL_EPI_RESID_F32 && (!q.aux || (q.aux_ld % 8)))) return PVRL_EINVAL;
-      GemmNT& p = g.prob[i];
-      p.A = (const op_t*)q.A; p.lda = q.lda; p.W = (const op_t*)q.W; p.ldw = q.ldw;
-      p.M = (int)q.M; p.N = (int)q.N; p.K = (int)q.K;
-      p.bias = q.bias; p.bias2 = nullptr; p.rowscale = q.rowscale; p.aux = q.aux; p.aux_ld = q.aux_ld; p.aux_rowmod = 0;
-      p.out0 = q.out0; p.ld0 = q.ld0; p.out1 = nullptr; p.ld1 = 0; p.m_off = 0;
-      p.cus = pvrl_compute_cus_per_xcd(); p.tails = 0;
+      GemmNT& p = g.prob[i] = nt_problem(q, nullptr, 0, nullptr, 0, 0);
       p.tiles_n = p.N / 128; p.tiles_m = cdiv(p.M, 128); p.gm = NT_GM;
       p.nwg = 8 * cdiv(p.tiles_m, 8) * p.tiles_n;
       g.first[i] = blocks;
       blocks += p.nwg;
     }
     g.first[g.n] = blocks;
-    switch (epilogue) {
-      case PVRL_EPI_BF16: hipLaunchKernelGGL(gemm_nt_batched_kernel<PVRL_EPI_BF16>, dim3(blocks), dim3(256), 0, s, g); break;
-      case PVRL_EPI_F32: hipLaunchKernelGGL(gemm_nt_batched_kernel<PVRL_EPI_F32>, dim3(blocks), dim3(256), 0, s, g); break;
-      default: hipLaunchKernelGGL(gemm_nt_batched_kernel<PVRL_EPI_RESID_F32>, dim3(blocks), dim3(256), 0, s, g); break;
-    }
+    with_epilogue<PVRL_EPI_BF16, PVRL_EPI_F32, PVRL_EPI_RESID_F32>(epilogue, [&](auto e) {     // (checked above)
+      hipLaunchKernelGGL(gemm_nt_batched_kernel<decltype(e)::value>, dim3(blocks), dim3(256), 0, s, g);
+      return PVRL_OK;
+    });
     PVRL_LAUNCH_CHECK();
   }
   return PVRL_OK;

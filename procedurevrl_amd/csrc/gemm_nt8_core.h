@@ -24,12 +24,7 @@
 //   * the ragged last round (L = tiles mod CUs per XCD): when 2 L <= CUs, those tiles are cut into two 128-row halves, one
 //     workgroup each: a half item is the upper half-tile A0 only, phases 0 and 1 of every K-tile, both waves of every SIMD busy.
 //
-// Hazards (wave groups G0 = waves 0-3, G1 = waves 4-7, G1 one barrier behind; every phase has a barrier after the memory and
-// after the compute segment):
-//   RAW  a half-tile is read in the phase AFTER the one whose memory segment waited for it (vmcnt) -- by then both groups have
-//        passed a barrier behind their wait;
-//   WAR  a half-tile is re-staged in the phase AFTER its last read, and every memory segment ends with lgkmcnt(0) BEFORE its
-//        barrier: when G0 issues the DMA, G1's reads of the previous phase have completed behind that barrier.
+// The segment ends and the RAW / WAR hazard argument of the two wave groups: gemm_shared.h (PP_BARRIER, PP_MEM_END, PP_CMP_END).
 // Replaces lib/models/vit.py:54-60,75-92,133 (nn.Linear forward + data gradient at the 50k-row shapes).
 #pragma once
 #include "gemm_nt_core.h"
@@ -54,42 +49,11 @@ __host__ __device__ inline Nt8Plan nt8_plan(int cm, int tiles_n, int cus, int en
   return t;
 }
 
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-// One 1 KiB LDS-DMA copy through a buffer descriptor: lane l's 16 bytes at r.base + soff + voff land at LDS byte lds + 16 l.
-// Offsets past the descriptor's size read as zero (the rows behind M of the ragged last panel).  Raw ISA: the compiler neither
-// counts it nor waits for it.  (s_nop 4: a descriptor / offset register produced by v_readfirstlane needs five wait states before
-// a vector-memory instruction reads it; s_nop 0: M0 write -> LDS-DMA.  Nothing inside an asm string is padded by hipcc.)
-__device__ __forceinline__ void bdma16(rsrc_t r, unsigned voff, unsigned soff, unsigned lds) {
-  asm volatile("s_nop 4\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds"
-               :: "v"(voff), "s"(r), "s"(soff), "s"(lds) : "memory", "m0");
-}
-#pragma clang diagnostic pop
-
 // row tiles whose residual / pre-activation loads go out together in the epilogue: four everywhere (two round trips per wave and
 // tile) except the fp32-residual epilogue, whose 64 residual registers next to 128 accumulators, 16 bias values and the second bias
 // do not fit 256 (measured by the compiler: 2 registers in scratch)
 template <int EPI>
 constexpr int NT8_EB = EPI == PVRL_EPI_RESID_F32 ? 2 : 4;
-
-#define NT8_BARRIER()                       \
-  do {                                      \
-    __builtin_amdgcn_sched_barrier(0);      \
-    __builtin_amdgcn_s_barrier();           \
-    __builtin_amdgcn_sched_barrier(0);      \
-  } while (0)
-// end of a memory segment: this wave's fragment reads have completed BEFORE the barrier (WAR rule above)
-#define NT8_MEM_END()                                     \
-  do {                                                    \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    \
-    NT8_BARRIER();                                        \
-    __builtin_amdgcn_s_setprio(1);                        \
-  } while (0)
-#define NT8_CMP_END()                 \
-  do {                                \
-    __builtin_amdgcn_s_setprio(0);    \
-    NT8_BARRIER();                    \
-  } while (0)
 
 template <int EPI>
 __global__ __launch_bounds__(512, 2) void gemm_nt8_kernel(GemmNT p) {
@@ -132,14 +96,14 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8_kernel(GemmNT p) {
     const int row = 16 * wave + 8 * e + (lane >> 3), pc = lane & 7;
 #pragma unroll
     for (int h = 0; h < 2; ++h) voffA[h][e] = (unsigned)(128 * h + row) * (unsigned)p.lda * 2u + ((unsigned)(pc ^ swz_x(row)) << 4);
-    voffW[e] = (unsigned)row * (unsigned)p.ldw * 2u + ((unsigned)(pc ^ swz_w<F32OUT>(row)) << 4);
+    voffW[e] = (unsigned)row * (unsigned)p.ldw * 2u + ((unsigned)(pc ^ swz_w(row)) << 4);
   }
   const unsigned wstep = 128u * (unsigned)p.ldw * 2u;       // W half-tile 1 starts 128 rows further
   // fragment byte offsets inside a half-tile (k-half 0; k-half 1 is ^ 64): row r at 128 r, chunk ^ swizzle(r); both swizzles are
   // periodic over the rows one lane reads (x: r + 16 t; w: r + 4 h), so one register per operand
   const int q = lane >> 4, i = lane & 15;
   const int rx = 64 * wm + i, rw = 32 * wn + 8 * (i >> 2) + (i & 3);
-  const int xb = rx * 128 + ((q ^ swz_x(rx)) << 4), wb = rw * 128 + ((q ^ swz_w<F32OUT>(rw)) << 4);
+  const int xb = rx * 128 + ((q ^ swz_x(rx)) << 4), wb = rw * 128 + ((q ^ swz_w(rw)) << 4);
 
   auto srdA = [&](int m0_, int maxrows) {                   // rows [m0_, m0_ + maxrows) of A, clipped at M
     const int rows = min(maxrows, p.M - m0_);
@@ -236,10 +200,10 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8_kernel(GemmNT p) {
       issueW(0, l0, cW, 0); issueA(0, l0, cA, 0); issueW(1, l0, cW, 0); issueA(1, l0, cA, 0);
       issueW(0, l1, cW, 128); issueA(0, l1, cA, 128); issueW(1, l1, cW, 128);
       asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-      NT8_BARRIER();
+      PP_BARRIER();
     }
     zero_acc();
-    if (wm == 1) NT8_BARRIER();                             // G1 runs one barrier interval behind G0
+    if (wm == 1) PP_BARRIER();                             // G1 runs one barrier interval behind G0
     for (int kt = 0; kt < nk; ++kt) {
       // The load stream, two cursors: the lower-row half-tile A1 of K-tile kt + 1 (its slot is free behind phase 3 of K-tile kt - 1)
       // and A0 / B0 / B1 of K-tile kt + 2 (this K-tile's slot, free behind phase 1) -- of this tile or, past its end, of the next.
@@ -265,10 +229,10 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8_kernel(GemmNT p) {
       } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
-      NT8_MEM_END();
+      PP_MEM_END();
       mmk(acc[0], 0);
       mmk(acc[0], 1);
-      NT8_CMP_END();
+      PP_CMP_END();
       rdAk(rbuf, 1, 0); rdAk(rbuf, 1, 1);
       if (on2) {
         issueW1(0, 0, lb, w2, so2); issueW1(0, 1, lb, w2, so2); issueA1(0, 0, lb, a2, so2);
@@ -278,12 +242,12 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8_kernel(GemmNT p) {
       } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
-      NT8_MEM_END();
+      PP_MEM_END();
       mmk(acc[1], 0);
       mmk(acc[1], 1);
-      NT8_CMP_END();
+      PP_CMP_END();
     }
-    if (wm == 0) NT8_BARRIER();                             // G0 waits for G1's last compute segment: both groups run the epilogue together
+    if (wm == 0) PP_BARRIER();                             // G0 waits for G1's last compute segment: both groups run the epilogue together
     nt_epilogue_at<EPI, EB>(p, acc[0], m0, n0, 64 * wm, 32 * wn, 128 + 32 * wn, lane);
     nt_epilogue_at<EPI, EB>(p, acc[1], m0, n0, 128 + 64 * wm, 32 * wn, 128 + 32 * wn, lane);
     par = (par + nk) & 1;
@@ -307,10 +271,10 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8_kernel(GemmNT p) {
       if (nk > 1) { issueW(0, l1, lsW, 128); issueA(0, l1, lsA, 128); }
       if (nk > 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      NT8_BARRIER();
+      PP_BARRIER();
     }
     zero_acc();
-    if (wm == 1) NT8_BARRIER();
+    if (wm == 1) PP_BARRIER();
     for (int kt = 0; kt < nk; ++kt) {
       const int cur = (par + kt) & 1;
       const char* rbuf = smem + cur * NT8_BUF;
@@ -319,9 +283,9 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8_kernel(GemmNT p) {
       if (kt + 1 < nk) issueW(1, lo, lsW, (unsigned)(kt + 1) * 128u);        // B1 of the other slot: last read in phase 1 of K-tile - 1
       rdA(rbuf, 0);
       rdB(rbuf, 0, rb0);
-      NT8_MEM_END();
+      PP_MEM_END();
       quad(acc[0], 0, rb0);
-      NT8_CMP_END();
+      PP_CMP_END();
       // ---- phase 1 ----
       if (kt + 2 < nk) {
         issueW(0, lb, lsW, (unsigned)(kt + 2) * 128u);
@@ -331,11 +295,11 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8_kernel(GemmNT p) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
       rdB(rbuf, 1, rb1);
-      NT8_MEM_END();
+      PP_MEM_END();
       quad(acc[0], 1, rb1);
-      NT8_CMP_END();
+      PP_CMP_END();
     }
-    if (wm == 0) NT8_BARRIER();
+    if (wm == 0) PP_BARRIER();
     nt_epilogue_at<EPI, EB>(p, acc[0], m0, n0, 64 * wm, 32 * wn, 128 + 32 * wn, lane);
   }
 }

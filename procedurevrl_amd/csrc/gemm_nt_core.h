@@ -19,7 +19,7 @@
 // epilogue streams 16-/32-/64-byte contiguous pieces per lane.
 #pragma once
 #include <algorithm>
-#include "common.h"
+#include "gemm_shared.h"
 #include "../../include/pvrl.h"
 
 namespace {
@@ -54,22 +54,17 @@ __device__ __forceinline__ int swz_x(int row) { return (row >> 1) & 7; }
 // W rows are read in a permuted order so that the lanes of one epilogue store instruction write contiguous bytes:
 //   tile nt = 2c + h holds column 32c + 8q + 4h + r -> a lane owns 8 consecutive columns (tiles 2c, 2c+1) and the 4 lanes
 //   q of a row cover 32 consecutive columns: 64 B of bf16 per store instruction, or a whole 128-byte line of fp32 in
-//   two back-to-back 16-byte stores per lane (the earlier natural order for fp32 wrote 64-byte half lines).
-// Each order has its own chunk swizzle making ds_read_b128 conflict-free (rows that a lane group reads together
-// must land on distinct 16-byte slots of the 256-byte bank row).
-template <bool F32OUT> __device__ __forceinline__ int w_row(int nt, int i) {
-  return 32 * (nt >> 1) + 8 * (i >> 2) + 4 * (nt & 1) + (i & 3);
-}
-template <bool F32OUT> __device__ __forceinline__ int swz_w(int row) {
-  return ((row >> 1) & 1) | (((row >> 3) & 3) << 1);
-}
+//   two back-to-back 16-byte stores per lane (an earlier natural order for fp32 wrote 64-byte half lines).
+// Its chunk swizzle makes ds_read_b128 conflict-free (rows that a lane group reads together must land on distinct 16-byte
+// slots of the 256-byte bank row).
+__device__ __forceinline__ int w_row(int nt, int i) { return 32 * (nt >> 1) + 8 * (i >> 2) + 4 * (nt & 1) + (i & 3); }
+__device__ __forceinline__ int swz_w(int row) { return ((row >> 1) & 1) | (((row >> 3) & 3) << 1); }
 
 // ---- cache policy of the epilogue's memory traffic: the default.  An epilogue GEMM streams hundreds of MB exactly once -- the
 // fp32 residual / stored pre-activation in, the outputs out (consumed by a LATER kernel) -- through a 4 MiB XCD L2 that should be
 // holding the W tiles and A panels the main loop re-reads, but written-through `sc1` stores and streaming `nt` loads (gfx950
 // `aux` bits of the raw buffer instructions) were swept on MI355X and every combination was slower than the default policy
 // (profiles/r3_nt_cache_policy.txt).
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
 // descriptor over `rows` rows of a row-major matrix starting at `base` (all arguments wave-uniform: kernel arguments and
 // blockIdx-derived tile origins).  Offsets past the last row are dropped (stores) / read as zero (loads) by the hardware
 // bounds check: the ragged last M-tile needs no per-row guard.
@@ -102,32 +97,48 @@ __device__ __forceinline__ void nt_epilogue_at(const GemmNT& p, f32x4 (&acc)[4][
   const int q = lane >> 4, i = lane & 15;
   const int ncol[2] = {n0 + c0 + 8 * q, n0 + c1 + 8 * q};   // this lane's first column of each 32-column group
   const int rows = __builtin_amdgcn_readfirstlane(max(0, min(1024, p.M - m0)));    // rows of the matrices from the tile's first row on (any bound >= the tile height that keeps the byte count in 31 bits)
+  // lane holds, for c = 0,1: columns ncol[c] + (0..7)  (tile 2c -> +0..3, tile 2c+1 -> +4..7); their bias, as the float4s of the
+  // fp32 stores (bv4[nt]) or as scalars (bv[c][0..7])
+  f32x4 bv4[4];
+  float bv[2][8];
   if constexpr (F32OUT) {
-    // lane holds, for c = 0,1: columns ncol[c] + (0..7)  (tile 2c -> +0..3, tile 2c+1 -> +4..7)
-    f32x4 bv[4];
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt)
-      bv[nt] = !p.bias ? (f32x4){0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(p.bias + ncol[nt >> 1] + 4 * (nt & 1));
-    // Per-row factors (DropPath) and the second bias are fetched HERE, before the first store: a load issued between the
-    // stores is followed by s_waitcnt vmcnt(0), and on gfx9 that also waits for every earlier store to be acknowledged by
-    // L2 -- four (rowscale) to sixteen (bias2) serial store round trips per thread.  bias2 has no 16 spare registers in the
-    // 128-VGPR budget of the 16-wave tile: each lane keeps ONE column of the block's 64 and the others come by ds_bpermute.
-    float rs4[4];
+      bv4[nt] = !p.bias ? (f32x4){0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(p.bias + ncol[nt >> 1] + 4 * (nt & 1));
+  } else {
 #pragma unroll
-    for (int mt = 0; mt < 4; ++mt) rs4[mt] = p.rowscale ? p.rowscale[min(m0 + rb + mt * 16 + i, p.M - 1)] : 1.f;
-    float b2lane = 0.f;
-    if constexpr (EPI == PVRL_EPI_RESID_F32) {
-      if (p.bias2) {
-        b2lane = p.bias2[n0 + (lane < 32 ? c0 + lane : c1 + lane - 32)];
-        if (!p.rowscale) {                 // no row factor: rs * (acc + bias) + bias2 = acc + (bias + bias2)
+    for (int c = 0; c < 2; ++c)
 #pragma unroll
-          for (int nt = 0; nt < 4; ++nt)
+      for (int e = 0; e < 8; ++e) bv[c][e] = !p.bias ? 0.f : p.bias[ncol[c] + e];
+  }
+  // Per-row factors (DropPath) and the second bias are fetched HERE, before the first store: a load issued between the
+  // stores is followed by s_waitcnt vmcnt(0), and on gfx9 that also waits for every earlier store to be acknowledged by
+  // L2 -- four (rowscale) to sixteen (bias2) serial store round trips per thread.  bias2 has no 16 spare registers in the
+  // 128-VGPR budget of the 16-wave tile: each lane keeps ONE column of the block's 64 and the others come by ds_bpermute
+  // (b2_src: the lane that keeps column e of this lane's 8 in column group c).
+  constexpr bool B2 = EPI == PVRL_EPI_RESID_F32 || EPI == PVRL_EPI_RESID_16;
+  float rs4[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) bv[nt][e] += __shfl(b2lane, 32 * (nt >> 1) + 8 * q + 4 * (nt & 1) + e, 64);
-        }
+  for (int mt = 0; mt < 4; ++mt) rs4[mt] = p.rowscale ? p.rowscale[min(m0 + rb + mt * 16 + i, p.M - 1)] : 1.f;
+  auto b2_src = [&](int c, int e) { return 32 * c + 8 * q + e; };
+  float b2lane = 0.f;
+  if constexpr (B2) {
+    if (p.bias2) {
+      b2lane = p.bias2[n0 + (lane < 32 ? c0 + lane : c1 + lane - 32)];
+      if (!p.rowscale) {                 // no row factor: rs * (acc + bias) + bias2 = acc + (bias + bias2)
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const float b2 = __shfl(b2lane, b2_src(c, e), 64);
+            if constexpr (F32OUT) bv4[2 * c + (e >> 2)][e & 3] += b2;
+            else bv[c][e] += b2;
+          }
       }
     }
-    const bool b2_late = EPI == PVRL_EPI_RESID_F32 && p.bias2 && p.rowscale;
+  }
+  const bool b2_late = B2 && p.bias2 && p.rowscale;
+  if constexpr (F32OUT) {
     const rsrc_t ro = tile_rsrc(p.out0, m0, p.ld0, 4, rows);
     // the residual: rows of the tile (streamed once: LD policy), or rows modulo aux_rowmod of a small table every clip
     // re-reads (pos / time embedding prologue: default policy)
@@ -163,12 +174,12 @@ __device__ __forceinline__ void nt_epilogue_at(const GemmNT& p, f32x4 (&acc)[4][
         for (int nt = 0; nt < 4; ++nt) {
           f32x4 ov;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) ov[e] = rs * (acc[mt][nt][e] + bv[nt][e]);
+          for (int e = 0; e < 4; ++e) ov[e] = rs * (acc[mt][nt][e] + bv4[nt][e]);
           if constexpr (EPI == PVRL_EPI_RESID_F32) {
             ov += rv[h][nt];
             if (b2_late) {
 #pragma unroll
-              for (int e = 0; e < 4; ++e) ov[e] += __shfl(b2lane, 32 * (nt >> 1) + 8 * q + 4 * (nt & 1) + e, 64);
+              for (int e = 0; e < 4; ++e) ov[e] += __shfl(b2lane, b2_src(nt >> 1, 4 * (nt & 1) + e), 64);
             }
           }
           bst16(ro, ob + (unsigned)(ncol[nt >> 1] + 4 * (nt & 1)) * 4u, ov);   // rows past M: dropped by the bounds check
@@ -176,15 +187,6 @@ __device__ __forceinline__ void nt_epilogue_at(const GemmNT& p, f32x4 (&acc)[4][
       }
     }
   } else {
-    // lane holds, for c = 0,1: columns ncol[c] + (0..7)  (tile 2c -> +0..3, tile 2c+1 -> +4..7)
-    float bv[2][8];
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) bv[c][e] = !p.bias ? 0.f : p.bias[ncol[c] + e];
-    float rs4[4];                      // before the first store (see above)
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) rs4[mt] = p.rowscale ? p.rowscale[min(m0 + rb + mt * 16 + i, p.M - 1)] : 1.f;
     constexpr bool TWO = EPI == PVRL_EPI_GELU || EPI == PVRL_EPI_QGELU;
     constexpr bool DACT = EPI == PVRL_EPI_DGELU || EPI == PVRL_EPI_DQGELU;
     // PVRL_EPI_RESID_16 (round 6): the residual add on the 16-bit patch rows of the split residual stream -- out = aux + rs * (acc +
@@ -193,19 +195,6 @@ __device__ __forceinline__ void nt_epilogue_at(const GemmNT& p, f32x4 (&acc)[4][
     // launch per step: its loads go out row tile by row tile).
     constexpr bool RES16 = EPI == PVRL_EPI_RESID_16;
     constexpr bool tab = RES16 && TAB;
-    float b2lane = 0.f;      // the second bias: each lane keeps ONE column of the block's 64, the others come by ds_bpermute (see above)
-    if constexpr (RES16) {
-      if (p.bias2) {
-        b2lane = p.bias2[n0 + (lane < 32 ? c0 + lane : c1 + lane - 32)];
-        if (!p.rowscale) {                 // no row factor: rs * (acc + bias) + bias2 = acc + (bias + bias2)
-#pragma unroll
-          for (int c = 0; c < 2; ++c)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) bv[c][e] += __shfl(b2lane, 32 * c + 8 * q + e, 64);
-        }
-      }
-    }
-    const bool b2_late = RES16 && p.bias2 && p.rowscale;
     const rsrc_t r0 = tile_rsrc(p.out0, m0, p.ld0, 2, rows);
     const rsrc_t r1 = TWO ? tile_rsrc(p.out1, m0, p.ld1, 2, rows) : r0;
     const rsrc_t ra = (DACT || RES16) ? (tab ? tile_rsrc(p.aux, 0, p.aux_ld, 4, p.aux_rowmod) : tile_rsrc(p.aux, m0, p.aux_ld, 2, rows)) : r0;
@@ -281,7 +270,7 @@ __device__ __forceinline__ void nt_epilogue_at(const GemmNT& p, f32x4 (&acc)[4][
             }
             if (b2_late) {          // (one branch, its eight ds_bpermute in flight together)
 #pragma unroll
-              for (int e = 0; e < 8; ++e) a[e] += __shfl(b2lane, 32 * c + 8 * q + e, 64);
+              for (int e = 0; e < 8; ++e) a[e] += __shfl(b2lane, b2_src(c, e), 64);
             }
             opx8 o0;
 #pragma unroll
@@ -349,7 +338,6 @@ __host__ __device__ inline NtTail nt_tail_plan(int cm, int tiles_n, int cus, int
 template <int EPI, int WM, int WN>
 __device__ __forceinline__ void gemm_nt_body(const GemmNT& p, const int bid) {
   constexpr int BM = 64 * WM, BN = 64 * WN, NW = WM * WN;
-  constexpr bool F32OUT = (EPI == PVRL_EPI_RESID_F32 || EPI == PVRL_EPI_F32);
   constexpr bool TAILS = WM == 4 && WN == 4;      // sub-tiles of the last round: 256x256 tiles only
   constexpr int XBYTES = BM * BK * 2, WBYTES = BN * BK * 2, STAGE = XBYTES + WBYTES;
   constexpr int NINST = (BM + BN) / 8;          // 1 KiB LDS-DMA instructions per stage
@@ -412,7 +400,7 @@ __device__ __forceinline__ void gemm_nt_body(const GemmNT& p, const int bid) {
       gsrc[j] = p.A + (long)grow * p.lda + ((pc ^ swz_x(row)) << 3);
     } else {
       const int row = ((gval[j] ? it : bm / 8) - bm / 8) * 8 + (lane >> 3);
-      gsrc[j] = p.W + (long)(n0 + row) * p.ldw + ((pc ^ swz_w<F32OUT>(row)) << 3);
+      gsrc[j] = p.W + (long)(n0 + row) * p.ldw + ((pc ^ swz_w(row)) << 3);
     }
   }
   auto stage = [&](int buf, int k0) {            // full tiles: two slots, the compiler orders the LDS-DMA (vmcnt(0) at the barrier)
@@ -432,8 +420,8 @@ __device__ __forceinline__ void gemm_nt_body(const GemmNT& p, const int bid) {
     for (int t = 0; t < 4; ++t) {
       const int rx = wm * 64 + t * 16 + i;
       xoff[t] = rx * 128 + ((q ^ swz_x(rx)) << 4);
-      const int rw = wn * 64 + w_row<F32OUT>(t, i);
-      woff[t] = rw * 128 + ((q ^ swz_w<F32OUT>(rw)) << 4);
+      const int rw = wn * 64 + w_row(t, i);
+      woff[t] = rw * 128 + ((q ^ swz_w(rw)) << 4);
     }
   }
 
@@ -540,10 +528,7 @@ constexpr int NT_BATCH_MAX = 12;
 struct GemmNTBatch { int n; int first[NT_BATCH_MAX + 1]; GemmNT prob[NT_BATCH_MAX]; };
 template <int EPI>
 __global__ __launch_bounds__(256) void gemm_nt_batched_kernel(GemmNTBatch g) {
-  int q = 0;
-#pragma unroll
-  for (int t = 1; t < NT_BATCH_MAX; ++t)
-    if (t < g.n && (int)blockIdx.x >= g.first[t]) q = t;
+  const int q = group_slot(g.first, g.n, (int)blockIdx.x);
   gemm_nt_body<EPI, 2, 2>(g.prob[q], (int)blockIdx.x - g.first[q]);
 }
 

@@ -15,6 +15,24 @@ bool tn_use_tn8(int64_t N, int64_t K, int64_t slice_rows, int64_t ldp, int64_t l
   return (N % 256 == 0) && (K % 256 == 0) && (slice_rows + 64) * std::max(ldp, ldq) * 2 < (int64_t(1) << 31) - 4096;
 }
 
+// One problem's kernel argument.  `ws` is its workspace: [splits][N][K] partials, then [splits][N] column sums (kept when q.dbias).
+// rt: 256 x 256 tiles and the (slice, tile) pair list of the one-round kernels (a grouped launch deals its pairs by TnGroup::per_xcd,
+// not by Ms_pairs); otherwise the 128 x 128 tiles of gemm_tn_kernel.
+GemmTN tn_problem(const pvrl_tn_problem& q, int64_t splits, float* ws, bool rt) {
+  GemmTN p = {};
+  p.P = (const op_t*)q.P; p.ldp = q.ldp; p.Q = (const op_t*)q.Q; p.ldq = q.ldq;
+  p.M = (int)q.M; p.N = (int)q.N; p.K = (int)q.K;
+  p.Ms = cdiv(cdiv(q.M > 0 ? q.M : 1, splits), TM) * TM;
+  p.part = ws;
+  p.cpart = q.dbias ? ws + splits * q.N * q.K : nullptr;
+  const int tile = rt ? 256 : 128;
+  p.tiles_k = cdiv(q.K, tile);
+  p.tiles_nk = cdiv(q.N, tile) * p.tiles_k;
+  p.npairs = (int)splits * p.tiles_nk;
+  p.Ms_pairs = cdiv(p.npairs, 8);
+  return p;
+}
+
 }  // namespace
 
 extern "C" int64_t pvrl_gemm_tn_plan_splits(int64_t M, int64_t N, int64_t K) {
@@ -75,28 +93,12 @@ int gemm_tn_impl(const void* P, int64_t ldp, const void* Q, int64_t ldq, int64_t
   if (!use_rt && (splits < 8 || (splits % 8))) return PVRL_EINVAL;   // slice s lives on XCD s % 8 in those kernels
   if ((ldp % 8) || (ldq % 8) || ((uintptr_t)P % 16) || ((uintptr_t)Q % 16)) return PVRL_EINVAL;
   if (workspace_bytes < pvrl_gemm_tn_workspace_bytes(N, K, splits)) return PVRL_EINVAL;
-  GemmTN p;
-  p.P = (const op_t*)P; p.ldp = ldp; p.Q = (const op_t*)Q; p.ldq = ldq;
-  p.M = (int)M; p.N = (int)N; p.K = (int)K;
-  int ms = cdiv(M > 0 ? M : 1, splits);
-  p.Ms = cdiv(ms, TM) * TM;
-  p.part = (float*)workspace;
-  p.cpart = dbias ? p.part + splits * N * K : nullptr;
+  GemmTN p = tn_problem({P, ldp, Q, ldq, M, N, K, beta, dW, dbias, gscale, nonfinite}, splits, (float*)workspace, use_rt);
+  p.zero_page = (const op_t*)((char*)workspace + splits * (N * K + N) * (int64_t)sizeof(float));
   hipStream_t s = (hipStream_t)stream;
-  char* zp = (char*)workspace + splits * (N * K + N) * (int64_t)sizeof(float);
-  p.zero_page = (const op_t*)zp;
-  if (use_rt) {
-    p.tiles_k = (int)cdiv(K, 256);
-    p.tiles_nk = (int)cdiv(N, 256) * p.tiles_k;
-    p.npairs = (int)splits * p.tiles_nk;
-    p.Ms_pairs = cdiv(p.npairs, 8);
-    if (tn_use_tn8(N, K, p.Ms, ldp, ldq)) hipLaunchKernelGGL(gemm_tn8_kernel, dim3((unsigned)(8 * p.Ms_pairs)), dim3(512), 0, s, p);
-    else hipLaunchKernelGGL(gemm_tn_rt8_kernel, dim3((unsigned)(8 * p.Ms_pairs)), dim3(512), 0, s, p);
-  } else {
-    p.tiles_k = (int)(K / 128);
-    p.tiles_nk = (int)(N / 128) * p.tiles_k;
-    hipLaunchKernelGGL((gemm_tn_kernel<2, 2>), dim3((unsigned)(splits * p.tiles_nk)), dim3(256), 0, s, p);
-  }
+  if (!use_rt) hipLaunchKernelGGL((gemm_tn_kernel<2, 2>), dim3((unsigned)(splits * p.tiles_nk)), dim3(256), 0, s, p);
+  else if (tn_use_tn8(N, K, p.Ms, ldp, ldq)) hipLaunchKernelGGL(gemm_tn8_kernel, dim3((unsigned)(8 * p.Ms_pairs)), dim3(512), 0, s, p);
+  else hipLaunchKernelGGL(gemm_tn_rt8_kernel, dim3((unsigned)(8 * p.Ms_pairs)), dim3(512), 0, s, p);
   PVRL_LAUNCH_CHECK();
   const long NK = N * K;
   const long nthreads = (NK >> 2) + (dbias ? N : 0);
@@ -178,21 +180,10 @@ extern "C" int pvrl_gemm_tn_grouped_bf16(int nprob, const pvrl_tn_problem* probl
   int first = 0;
   for (int i = 0; i < nprob; ++i) {
     const pvrl_tn_problem& q = problems[i];
-    GemmTN& p = g.prob[i];
-    p.P = (const op_t*)q.P; p.ldp = q.ldp; p.Q = (const op_t*)q.Q; p.ldq = q.ldq;
-    p.M = (int)q.M; p.N = (int)q.N; p.K = (int)q.K;
-    p.Ms = cdiv(cdiv(q.M, splits), TM) * TM;
-    p.part = w;
-    w += splits * q.N * q.K;
-    p.cpart = q.dbias ? w : nullptr;
-    w += splits * q.N;
-    p.zero_page = nullptr;
-    p.tiles_k = (int)cdiv(q.K, 256);
-    p.tiles_nk = (int)cdiv(q.N, 256) * p.tiles_k;
-    p.npairs = (int)splits * p.tiles_nk;
-    p.Ms_pairs = 0;
+    g.prob[i] = tn_problem(q, splits, w, true);
+    w += splits * (q.N * q.K + q.N);
     g.first[i] = first;
-    first += p.npairs;
+    first += g.prob[i].npairs;
   }
   g.first[nprob] = first;
   g.total = first;

@@ -15,7 +15,7 @@
 //   * waves 0-3 (one per SIMD) run one barrier interval ahead of waves 4-7: a stage is two phases (n half 0 / 1, both m halves), each
 //     a MEMORY segment (16-32 transposing reads into registers, the LDS-DMA instructions of the stage two ahead, the counted wait)
 //     and a COMPUTE segment (32 MFMAs on registers), so one wave of every SIMD computes while the other reads;
-//   * loads run two stages ahead with counted waits (vmcnt(8)), as in the NT kernel -- same hazard argument (gemm_nt8_core.h).
+//   * loads run two stages ahead with counted waits (vmcnt(8)), as in the NT kernel -- same hazard argument (gemm_shared.h).
 // Measured and dropped (profiles/r4_tn_ablation.txt): a ring of five 32-row stages (128 KiB in flight instead of 96: 3 % slower), one
 // descriptor per stage instead of the stage offset in the scalar offset (4 % slower), an L2 touch 3-6 stages ahead by the tile's first
 // reader in its XCD (7-10 % slower).
@@ -26,53 +26,19 @@
 
 namespace {
 
-typedef __amdgpu_buffer_rsrc_t tn_rsrc_t;
 constexpr int TN8_HALF = 64 * 128 * 2;   // one half-tile: 64 m x 128 columns x 2 B = 16 KiB, [m / 4][column / 16] blocks of 128 B
 constexpr int TN8_BUF = 4 * TN8_HALF;    // one stage: P0 P1 Q0 Q1
-
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-// one 1 KiB LDS-DMA copy through a buffer descriptor: lane l's 16 bytes at r.base + soff + voff land at LDS byte lds + 16 l; offsets
-// past the descriptor's size read as zero.  (s_nop 4: SGPRs written by v_readfirstlane -> vector-memory instruction; s_nop 0: M0.)
-__device__ __forceinline__ void tn8_dma16(tn_rsrc_t r, unsigned voff, unsigned soff, unsigned lds) {
-  asm volatile("s_nop 4\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds"
-               :: "v"(voff), "s"(r), "s"(soff), "s"(lds) : "memory", "m0");
-}
-#pragma clang diagnostic pop
-
-#define TN8_BARRIER()                       \
-  do {                                      \
-    __builtin_amdgcn_sched_barrier(0);      \
-    __builtin_amdgcn_s_barrier();           \
-    __builtin_amdgcn_sched_barrier(0);      \
-  } while (0)
-// end of a memory segment: this wave's fragment reads have completed BEFORE the barrier (the slot they came from may be re-staged
-// by the other group right behind it)
-#define TN8_MEM_END()                                     \
-  do {                                                    \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    \
-    TN8_BARRIER();                                        \
-    __builtin_amdgcn_s_setprio(1);                        \
-  } while (0)
-#define TN8_CMP_END()                 \
-  do {                                \
-    __builtin_amdgcn_s_setprio(0);    \
-    TN8_BARRIER();                    \
-  } while (0)
 
 __device__ __forceinline__ void tn8_pair(const GemmTN& p, const int pair, char* smem) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
   const unsigned sbase = __builtin_amdgcn_readfirstlane(lds_addr(smem));
-  const int s = pair / p.tiles_nk;
-  const int rem = pair - s * p.tiles_nk;
-  const int tn = rem / p.tiles_k, tk = rem - tn * p.tiles_k;
-  const int n0 = tn * 256, k0 = tk * 256;
-  const int mbeg = s * p.Ms;
-  const int rows = min(p.M, mbeg + p.Ms) - mbeg;
+  int s, tk, n0, k0, mbeg, rows;
+  float* part;
+  tn_pair_tile(p, pair, s, tk, n0, k0);
+  tn_pair_slice(p, s, mbeg, rows, part);
   const int q = lane >> 4, i = lane & 15;
-  float* part = p.part + (long)s * p.N * p.K;
   const bool has_csum = p.cpart != nullptr && tk == 0;
   const bool do_csum = has_csum && wn == wm;               // waves 0 and 5 (two different SIMDs) sum the columns of their P fragments (VALU in the MFMAs' shadow)
   if (rows <= 0) {                                         // empty slice: its partial tile must still be zero
@@ -105,10 +71,10 @@ __device__ __forceinline__ void tn8_pair(const GemmTN& p, const int pair, char* 
   // descriptors over the slice's rows of the tile's 256 columns; the first byte behind (rows - 1, column 255) is out of range.  The stage
   // offset travels in the instruction's scalar offset, which gfx950 includes in the range check (tests/kernel_checks.py
   // check_gemm_tn_rows_behind_the_end); a descriptor per stage was measured 4 % slower (scalar work in every memory segment).
-  const tn_rsrc_t rP = __builtin_amdgcn_make_buffer_rsrc((void*)(p.P + (long)mbeg * p.ldp + n0), 0, (int)(((long)(rows - 1) * p.ldp + 256) * 2), 0x00020000);
-  const tn_rsrc_t rQ = __builtin_amdgcn_make_buffer_rsrc((void*)(p.Q + (long)mbeg * p.ldq + k0), 0, (int)(((long)(rows - 1) * p.ldq + 256) * 2), 0x00020000);
-  auto issueP1 = [&](int h, int e, unsigned lb, unsigned soff) { tn8_dma16(rP, voffP[h][e], soff, lb + h * TN8_HALF + wave * 2048 + e * 1024); };
-  auto issueQ1 = [&](int c, int e, unsigned lb, unsigned soff) { tn8_dma16(rQ, voffQ[c][e], soff, lb + (2 + c) * TN8_HALF + wave * 2048 + e * 1024); };
+  const rsrc_t rP = __builtin_amdgcn_make_buffer_rsrc((void*)(p.P + (long)mbeg * p.ldp + n0), 0, (int)(((long)(rows - 1) * p.ldp + 256) * 2), 0x00020000);
+  const rsrc_t rQ = __builtin_amdgcn_make_buffer_rsrc((void*)(p.Q + (long)mbeg * p.ldq + k0), 0, (int)(((long)(rows - 1) * p.ldq + 256) * 2), 0x00020000);
+  auto issueP1 = [&](int h, int e, unsigned lb, unsigned soff) { bdma16(rP, voffP[h][e], soff, lb + h * TN8_HALF + wave * 2048 + e * 1024); };
+  auto issueQ1 = [&](int c, int e, unsigned lb, unsigned soff) { bdma16(rQ, voffQ[c][e], soff, lb + (2 + c) * TN8_HALF + wave * 2048 + e * 1024); };
   auto issueP = [&](int h, unsigned lb, unsigned soff) { issueP1(h, 0, lb, soff); issueP1(h, 1, lb, soff); };
   auto issueQ = [&](int c, unsigned lb, unsigned soff) { issueQ1(c, 0, lb, soff); issueQ1(c, 1, lb, soff); };
 
@@ -160,9 +126,9 @@ __device__ __forceinline__ void tn8_pair(const GemmTN& p, const int pair, char* 
     issueQ(0, l0, 0); issueP(0, l0, 0); issueQ(1, l0, 0); issueP(1, l0, 0);
     issueQ(0, l1, stepQ); issueP(0, l1, stepP); issueQ(1, l1, stepQ);
     asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    TN8_BARRIER();
+    PP_BARRIER();
   }
-  if (wm == 1) TN8_BARRIER();                              // waves 4-7 run one barrier interval behind waves 0-3
+  if (wm == 1) PP_BARRIER();                              // waves 4-7 run one barrier interval behind waves 0-3
   for (int kt = 0; kt < nk; ++kt) {
     // the load stream, two cursors: P1 of stage kt + 1 (its slot is free behind phase 3 of stage kt - 1) and P0 / Q0 / Q1 of
     // stage kt + 2 (this stage's slot, free behind phase 1)
@@ -181,10 +147,10 @@ __device__ __forceinline__ void tn8_pair(const GemmTN& p, const int pair, char* 
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    TN8_MEM_END();
+    PP_MEM_END();
     mmk(acc[0], 0, 0);
     mmk(acc[0], 0, 1);
-    TN8_CMP_END();
+    PP_CMP_END();
     rdP(rbuf, 1, 0); rdP(rbuf, 1, 1);
     if (on2) {
       issueQ1(0, 0, lb, sQ2); issueQ1(0, 1, lb, sQ2); issueP1(0, 0, lb, sP2);
@@ -193,12 +159,12 @@ __device__ __forceinline__ void tn8_pair(const GemmTN& p, const int pair, char* 
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    TN8_MEM_END();
+    PP_MEM_END();
     mmk(acc[1], 1, 0);
     mmk(acc[1], 1, 1);
-    TN8_CMP_END();
+    PP_CMP_END();
   }
-  if (wm == 0) TN8_BARRIER();                              // both groups leave the loop together
+  if (wm == 0) PP_BARRIER();                              // both groups leave the loop together
 
   // lane holds n = n0 + 128 mh + 64 wm + 16 t + i, k = k0 + 128 c + 32 wn + 16 h2 + 4 q + (0..3)
 #pragma unroll
@@ -224,22 +190,16 @@ __device__ __forceinline__ void tn8_pair(const GemmTN& p, const int pair, char* 
 
 __global__ __launch_bounds__(512, 2) void gemm_tn8_kernel(GemmTN p) {
   __shared__ __attribute__((aligned(16))) char smem[2 * TN8_BUF];
-  const int xcd = blockIdx.x & 7, jj = blockIdx.x >> 3;
-  const int pair = xcd * p.Ms_pairs + jj;
-  if (jj >= p.Ms_pairs || pair >= p.npairs) return;
-  tn8_pair(p, pair, smem);
+  int pair;
+  if (tn_block_pair(p.Ms_pairs, p.npairs, pair)) tn8_pair(p, pair, smem);
 }
 
 // several weight gradients in one launch (TnGroup, gemm_tn_core.h): every problem of the group has N % 256 == 0 and K % 256 == 0
 __global__ __launch_bounds__(512, 2) void gemm_tn8_grouped_kernel(TnGroup g) {
   __shared__ __attribute__((aligned(16))) char smem[2 * TN8_BUF];
-  const int xcd = blockIdx.x & 7, jj = blockIdx.x >> 3;
-  const int gp = xcd * g.per_xcd + jj;
-  if (jj >= g.per_xcd || gp >= g.total) return;
-  int q = 0;
-#pragma unroll
-  for (int t = 1; t < TN_GROUP_MAX; ++t)
-    if (t < g.nprob && gp >= g.first[t]) q = t;
+  int gp;
+  if (!tn_block_pair(g.per_xcd, g.total, gp)) return;
+  const int q = group_slot(g.first, g.nprob, gp);
   const GemmTN p = g.prob[q];
   tn8_pair(p, gp - g.first[q], smem);
 }

@@ -15,7 +15,7 @@
 // (deterministic, no atomics).  Block order is slice-major so the workgroups alive at
 // one time stream the same rows of P and Q through L2 / Infinity Cache.
 #pragma once
-#include "common.h"
+#include "gemm_shared.h"
 #include "../../include/pvrl.h"
 
 namespace {
@@ -223,6 +223,29 @@ __global__ __launch_bounds__(64 * WN * WK) void gemm_tn_kernel(GemmTN p) {
 // MEASURED (same-process A/B, M = 50,208): wfc1 233 vs 247 us, wfc2 237 vs 248, wqkv 189 vs 190, wproj 76 vs 80 against the
 // four-wave 32x32x16 kernel (knob 7); 57.1 vs 57.5 ms per training step -> the default (knob 0 / 8).
 // ---------------------------------------------------------------------------------------------------------
+// The work list of the one-round kernels (tn_rt8_pair here, tn8_pair in gemm_tn8_core.h): `total` (slice, tile) pairs in slice-major
+// order, dealt to the XCDs in contiguous chunks of per_xcd (hardware: block b -> XCD b % 8).  This block's pair; false: none.
+__device__ __forceinline__ bool tn_block_pair(int per_xcd, int total, int& pair) {
+  const int xcd = blockIdx.x & 7, jj = blockIdx.x >> 3;
+  pair = xcd * per_xcd + jj;
+  return jj < per_xcd && pair < total;
+}
+// A pair is (slice s, 256 x 256 tile): the tile's origin (n0, k0) in dW, tk its index along K ...
+__device__ __forceinline__ void tn_pair_tile(const GemmTN& p, int pair, int& s, int& tk, int& n0, int& k0) {
+  s = pair / p.tiles_nk;
+  const int rem = pair - s * p.tiles_nk;
+  const int tn = rem / p.tiles_k;
+  tk = rem - tn * p.tiles_k;
+  n0 = tn * 256; k0 = tk * 256;
+}
+// ... and the slice's rows [mbeg, mbeg + rows) of P and Q with its partial dW.  rows <= 0: an empty slice, whose partial tile (and
+// column sums) must still be written, as zeros.
+__device__ __forceinline__ void tn_pair_slice(const GemmTN& p, int s, int& mbeg, int& rows, float*& part) {
+  mbeg = s * p.Ms;
+  rows = min(p.M, mbeg + p.Ms) - mbeg;
+  part = p.part + (long)s * p.N * p.K;
+}
+
 constexpr int RT8_TS = 64;
 constexpr int RT8_OPB = 8 * 256 * 16;                      // 32 KiB per operand and stage: [m / 8][col][8 m]
 constexpr int RT8_STAGE = 2 * RT8_OPB;
@@ -231,10 +254,9 @@ __device__ __forceinline__ void tn_rt8_pair(const GemmTN& p, const int pair, cha
   constexpr int TS = RT8_TS, OPB = RT8_OPB, STAGE = RT8_STAGE;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int s = pair / p.tiles_nk;
-  const int rem = pair - s * p.tiles_nk;
-  const int tn = rem / p.tiles_k, tk = rem - tn * p.tiles_k;
-  const int n0 = tn * 256, k0 = tk * 256;
+  int s, tk, n0, k0, mbeg, rows;
+  float* part;
+  tn_pair_tile(p, pair, s, tk, n0, k0);
   // N and K are multiples of 128, not necessarily of 256: the last tile along either may be half a tile.  Its missing columns
   // are staged as zeros; the waves whose 128 x 64 block lies in the missing half only help with the staging -- no fragment
   // reads, no MFMAs, no stores (MViTv2-S: 96 / 384-wide layers, 11 of every 38 tiles of a stage-3 block are padding).  The wave
@@ -246,11 +268,8 @@ __device__ __forceinline__ void tn_rt8_pair(const GemmTN& p, const int pair, cha
   const int wk = remap ? (wave & 3) : (wave >> 1);
   const bool n_ok = nfull || wn == 0, k_ok = kfull || wk < 2;
   const bool compute = n_ok && k_ok;   // wave-uniform
-  const int mbeg = s * p.Ms;
-  const int mend = min(p.M, mbeg + p.Ms);
-  const int rows = mend - mbeg;
+  tn_pair_slice(p, s, mbeg, rows, part);
   const int q = lane >> 4, i = lane & 15;
-  float* part = p.part + (long)s * p.N * p.K;
   if (rows <= 0) {                                         // empty slice: its partial tile must still be zero
     if (n_ok && k_ok)
       for (int nt = 0; nt < 8; ++nt)
@@ -414,10 +433,8 @@ __device__ __forceinline__ void tn_rt8_pair(const GemmTN& p, const int pair, cha
 
 __global__ __launch_bounds__(512, 2) void gemm_tn_rt8_kernel(GemmTN p) {
   __shared__ __attribute__((aligned(16))) char smem[2 * RT8_STAGE];
-  const int xcd = blockIdx.x & 7, jj = blockIdx.x >> 3;
-  const int pair = xcd * p.Ms_pairs + jj;
-  if (jj >= p.Ms_pairs || pair >= p.npairs) return;
-  tn_rt8_pair(p, pair, smem);
+  int pair;
+  if (tn_block_pair(p.Ms_pairs, p.npairs, pair)) tn_rt8_pair(p, pair, smem);
 }
 
 // Several weight gradients in ONE launch: the (slice, tile) pairs of up to 8 problems are laid end to end and dealt to the
@@ -432,13 +449,9 @@ struct TnGroup {
 };
 __global__ __launch_bounds__(512, 2) void gemm_tn_rt8_grouped_kernel(TnGroup g) {
   __shared__ __attribute__((aligned(16))) char smem[2 * RT8_STAGE];
-  const int xcd = blockIdx.x & 7, jj = blockIdx.x >> 3;
-  const int gp = xcd * g.per_xcd + jj;
-  if (jj >= g.per_xcd || gp >= g.total) return;
-  int q = 0;
-#pragma unroll
-  for (int t = 1; t < TN_GROUP_MAX; ++t)
-    if (t < g.nprob && gp >= g.first[t]) q = t;
+  int gp;
+  if (!tn_block_pair(g.per_xcd, g.total, gp)) return;
+  const int q = group_slot(g.first, g.nprob, gp);
   const GemmTN p = g.prob[q];
   tn_rt8_pair(p, gp - g.first[q], smem);
 }
@@ -454,6 +467,41 @@ __device__ __forceinline__ void raise_if(bool bad, float* flag) {
   if (flag && __any(bad) && (threadIdx.x & 63) == 0) *flag = 1.f;
 }
 
+// The order in which the slices' partials are summed, kept once (tests/gemm_checks.py pins it bit for bit).  Each is an expression
+// that yields the sum: f32x4 for a weight float4, a scalar for a bias value.  (Macros: as inlined functions the same loops come out
+// with their blocks in another order, i.e. as different kernel binaries.)
+// SERIAL (tn_reduce_kernel, tn_reduce_grouped_kernel): one chain, slices 0, 1, 2 ...; the weights' chain starts from slice 0's
+// value, the bias' from 0.f.
+// FOUR CHAINS (tn_reduce_small_kernel, tn_reduce_into_kernel; 256 threads own 64 float4s, o_ = thread & 63): wave sl_ sums slices
+// sl_, sl_ + 4, ... from 0.f and the four are combined through LDS as (0 + 1) + (2 + 3).  Wave 0 gets the sum (the other waves their
+// own chain); a bias value (is_b) travels in element 0.
+#define TN_SUM_SERIAL_W(part, splits, NK, idx4)                                                                    \
+  ({                                                                                                               \
+    f32x4 a_ = reinterpret_cast<const f32x4*>(part)[idx4];                                                         \
+    for (int s_ = 1; s_ < (splits); ++s_) a_ += reinterpret_cast<const f32x4*>((part) + (long)s_ * (NK))[idx4];    \
+    a_;                                                                                                            \
+  })
+#define TN_SUM_SERIAL_B(cpart, splits, N, n)                                      \
+  ({                                                                              \
+    float a_ = 0.f;                                                               \
+    for (int s_ = 0; s_ < (splits); ++s_) a_ += (cpart)[(long)s_ * (N) + (n)];    \
+    a_;                                                                           \
+  })
+#define TN_SUM_CHAINS(part, cpart, splits, NK, N, idx4, is_w, is_b, o_, sl_)                                           \
+  ({                                                                                                                   \
+    __shared__ f32x4 red_[3][64];                                                                                      \
+    f32x4 a_ = (f32x4){0.f, 0.f, 0.f, 0.f};                                                                            \
+    if (is_w) {                                                                                                        \
+      for (int s_ = sl_; s_ < (splits); s_ += 4) a_ += reinterpret_cast<const f32x4*>((part) + (long)s_ * (NK))[idx4]; \
+    } else if (is_b) {                                                                                                 \
+      for (int s_ = sl_; s_ < (splits); s_ += 4) a_[0] += (cpart)[(long)s_ * (N) + (int)((idx4) - ((NK) >> 2))];       \
+    }                                                                                                                  \
+    if (sl_ > 0) red_[sl_ - 1][o_] = a_;                                                                               \
+    __syncthreads();                                                                                                   \
+    if (sl_ == 0) a_ = (a_ + red_[0][o_]) + (red_[1][o_] + red_[2][o_]);                                               \
+    a_;                                                                                                                \
+  })
+
 // out[n][k] = beta*out + gscale * sum_s part[s][n][k];  bias_out[n] = beta*bias_out + gscale * sum_s cpart[s][n]
 __global__ __launch_bounds__(256) void tn_reduce_kernel(const float* __restrict__ part, const float* __restrict__ cpart,
                                                         int splits, long NK, int N, float beta,
@@ -464,19 +512,14 @@ __global__ __launch_bounds__(256) void tn_reduce_kernel(const float* __restrict_
   const float gsc = gscale ? *gscale : 1.f;
   bool bad = false;
   if (idx4 < n4) {
-    f32x4 a = reinterpret_cast<const f32x4*>(part)[idx4];
-    for (int s = 1; s < splits; ++s) {
-      const f32x4 b = reinterpret_cast<const f32x4*>(part + (long)s * NK)[idx4];
-      a += b;
-    }
+    f32x4 a = TN_SUM_SERIAL_W(part, splits, NK, idx4);
     if (gscale) a *= gsc;
     if (beta != 0.f) a += beta * reinterpret_cast<f32x4*>(out)[idx4];
     reinterpret_cast<f32x4*>(out)[idx4] = a;
     bad = nonfinite4(a);
   } else if (bias_out && idx4 - n4 < N) {
     const int n = (int)(idx4 - n4);
-    float a = 0.f;
-    for (int s = 0; s < splits; ++s) a += cpart[(long)s * N + n];
+    float a = TN_SUM_SERIAL_B(cpart, splits, N, n);
     if (gscale) a *= gsc;
     if (beta != 0.f) a += beta * bias_out[n];
     bias_out[n] = a;
@@ -492,21 +535,12 @@ __global__ __launch_bounds__(256) void tn_reduce_small_kernel(const float* __res
                                                               int splits, long NK, int N, float beta,
                                                               float* __restrict__ out, float* __restrict__ bias_out,
                                                               const float* __restrict__ gscale, float* __restrict__ nonfinite) {
-  __shared__ f32x4 red[3][64];
   const int o = threadIdx.x & 63, sl = threadIdx.x >> 6;
   const long idx4 = (long)blockIdx.x * 64 + o;
   const long n4 = NK >> 2;
   const bool is_w = idx4 < n4, is_b = !is_w && bias_out && idx4 - n4 < N;
-  f32x4 a = (f32x4){0.f, 0.f, 0.f, 0.f};
-  if (is_w) {
-    for (int s = sl; s < splits; s += 4) a += reinterpret_cast<const f32x4*>(part + (long)s * NK)[idx4];
-  } else if (is_b) {
-    for (int s = sl; s < splits; s += 4) a[0] += cpart[(long)s * N + (int)(idx4 - n4)];
-  }
-  if (sl > 0) red[sl - 1][o] = a;
-  __syncthreads();
+  f32x4 a = TN_SUM_CHAINS(part, cpart, splits, NK, N, idx4, is_w, is_b, o, sl);
   if (sl == 0) {
-    a = (a + red[0][o]) + (red[1][o] + red[2][o]);
     if (gscale) a *= *gscale;
     bool bad = false;
     if (is_w) {
@@ -531,21 +565,12 @@ __global__ __launch_bounds__(256) void tn_reduce_into_kernel(const float* __rest
                                                              float* __restrict__ out, long ldo, int nv, int kv,
                                                              float* __restrict__ bias_out,
                                                              const float* __restrict__ gscale, float* __restrict__ nonfinite) {
-  __shared__ f32x4 red[3][64];
   const int o = threadIdx.x & 63, sl = threadIdx.x >> 6;
   const long idx4 = (long)blockIdx.x * 64 + o;
   const long n4 = NK >> 2;
   const bool is_w = idx4 < n4, is_b = !is_w && bias_out && idx4 - n4 < N;
-  f32x4 a = (f32x4){0.f, 0.f, 0.f, 0.f};
-  if (is_w) {
-    for (int s = sl; s < splits; s += 4) a += reinterpret_cast<const f32x4*>(part + (long)s * NK)[idx4];
-  } else if (is_b) {
-    for (int s = sl; s < splits; s += 4) a[0] += cpart[(long)s * N + (int)(idx4 - n4)];
-  }
-  if (sl > 0) red[sl - 1][o] = a;
-  __syncthreads();
+  f32x4 a = TN_SUM_CHAINS(part, cpart, splits, NK, N, idx4, is_w, is_b, o, sl);
   if (sl == 0) {
-    a = (a + red[0][o]) + (red[1][o] + red[2][o]);
     if (gscale) a *= *gscale;
     bool bad = false;
     if (is_w) {
@@ -584,10 +609,7 @@ struct TnReduceGroup {
   const float* gscale[TN_RED_MAX]; float* nonfinite[TN_RED_MAX];
 };
 __global__ __launch_bounds__(256) void tn_reduce_grouped_kernel(TnReduceGroup g) {
-  int q = 0;
-#pragma unroll
-  for (int t = 1; t < TN_RED_MAX; ++t)
-    if (t < g.nprob && (int)blockIdx.x >= g.first[t]) q = t;
+  const int q = group_slot(g.first, g.nprob, (int)blockIdx.x);
   const float* __restrict__ part = g.part[q];
   const float* __restrict__ cpart = g.cpart[q];
   float* __restrict__ out = g.out[q];
@@ -601,16 +623,14 @@ __global__ __launch_bounds__(256) void tn_reduce_grouped_kernel(TnReduceGroup g)
   const long n4 = NK >> 2;
   bool bad = false;
   if (idx4 < n4) {
-    f32x4 a = reinterpret_cast<const f32x4*>(part)[idx4];
-    for (int s = 1; s < g.splits; ++s) a += reinterpret_cast<const f32x4*>(part + (long)s * NK)[idx4];
+    f32x4 a = TN_SUM_SERIAL_W(part, g.splits, NK, idx4);
     if (gscale) a *= gsc;
     if (beta != 0.f) a += beta * reinterpret_cast<f32x4*>(out)[idx4];
     reinterpret_cast<f32x4*>(out)[idx4] = a;
     bad = nonfinite4(a);
   } else if (bias_out && idx4 - n4 < N) {
     const int n = (int)(idx4 - n4);
-    float a = 0.f;
-    for (int s = 0; s < g.splits; ++s) a += cpart[(long)s * N + n];
+    float a = TN_SUM_SERIAL_B(cpart, g.splits, N, n);
     if (gscale) a *= gsc;
     if (beta != 0.f) a += beta * bias_out[n];
     bias_out[n] = a;

@@ -10,7 +10,7 @@ LIB = os.path.join(HERE, "libpvrl_probe.so")
 def build(force=False):
     src = os.path.join(HERE, "gemm_variants.hip")
     csrc = os.path.join(HERE, "..", "..", "procedurevrl_amd", "csrc")
-    deps = [src] + [os.path.join(csrc, f) for f in ("gemm_nt_core.h", "gemm_tn_core.h", "common.h")]
+    deps = [src] + [os.path.join(csrc, f) for f in ("gemm_nt_core.h", "gemm_tn_core.h", "gemm_shared.h", "common.h")]
     if not force and os.path.exists(LIB) and os.path.getmtime(LIB) >= max(os.path.getmtime(d) for d in deps):
         return LIB
     cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-shared", "--offload-arch=gfx950", "-Wno-unused-result",

@@ -73,7 +73,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_persist_kernel(GemmNT p)
         gsrc[e] = p.A + (long)grow * p.lda + ((pc ^ swz_x(row)) << 3);
       } else {
         const int row = (it - BM / 8) * 8 + (lane >> 3);
-        gsrc[e] = p.W + (long)(n0 + row) * p.ldw + ((pc ^ swz_w<F32OUT>(row)) << 3);
+        gsrc[e] = p.W + (long)(n0 + row) * p.ldw + ((pc ^ swz_w(row)) << 3);
       }
     }
   };
@@ -89,8 +89,8 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_persist_kernel(GemmNT p)
     for (int t = 0; t < 4; ++t) {
       const int rx = wm * 64 + t * 16 + i;
       xoff[t] = rx * 128 + ((q ^ swz_x(rx)) << 4);
-      const int rw = wn * 64 + w_row<F32OUT>(t, i);
-      woff[t] = rw * 128 + ((q ^ swz_w<F32OUT>(rw)) << 4);
+      const int rw = wn * 64 + w_row(t, i);
+      woff[t] = rw * 128 + ((q ^ swz_w(rw)) << 4);
     }
   }
   const int nk = p.K / BK;
@@ -210,7 +210,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_w128_kernel(GemmNT p) {
       gsrc[j] = p.A + (long)grow * p.lda + ((pc ^ swz_x(row)) << 3);
     } else {
       const int row = (it - BM / 8) * 8 + (lane >> 3);
-      gsrc[j] = p.W + (long)(n0 + row) * p.ldw + ((pc ^ swz_w<F32OUT>(row)) << 3);
+      gsrc[j] = p.W + (long)(n0 + row) * p.ldw + ((pc ^ swz_w(row)) << 3);
     }
   }
   auto stage = [&](int buf, int k0) {
@@ -229,8 +229,8 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_w128_kernel(GemmNT p) {
     }
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      const int rw = wn * 64 + w_row<F32OUT>(t, i);
-      woff[t] = XBYTES + rw * 128 + ((q ^ swz_w<F32OUT>(rw)) << 4);
+      const int rw = wn * 64 + w_row(t, i);
+      woff[t] = XBYTES + rw * 128 + ((q ^ swz_w(rw)) << 4);
     }
   }
 
@@ -331,7 +331,7 @@ __global__ __launch_bounds__(1024) void gemm_nt_pipe_kernel(GemmNT p) {
     for (int t = 0; t < 4; ++t) {
       const int rx = wm * 64 + t * 16 + i;
       xoff[t] = rx * 64 + ((q ^ swz_x64(rx)) << 4);
-      const int rw = wn * 64 + w_row<F32OUT>(t, i);
+      const int rw = wn * 64 + w_row(t, i);
       woff[t] = XBYTES + rw * 64 + ((q ^ swz_w64<F32OUT>(rw)) << 4);
     }
   }
@@ -445,7 +445,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) / 2) void gemm_nt_ring_kern
     for (int t = 0; t < 4; ++t) {
       const int rx = wm * 64 + t * 16 + i;
       xoff[t] = rx * 64 + ((q ^ swz_x64(rx)) << 4);
-      const int rw = wn * 64 + w_row<F32OUT>(t, i);
+      const int rw = wn * 64 + w_row(t, i);
       woff[t] = XBYTES + rw * 64 + ((q ^ swz_w64<F32OUT>(rw)) << 4);
     }
   }
@@ -549,7 +549,7 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_w4_kernel(GemmNT p) {
     for (int t = 0; t < 8; ++t) {
       const int rx = wm * 128 + (t >> 2) * 64 + (t & 3) * 16 + i;
       xoff[t] = rx * 64 + ((q ^ swz_x64(rx)) << 4);
-      const int rw = wn * 128 + (t >> 2) * 64 + w_row<F32OUT>(t & 3, i);
+      const int rw = wn * 128 + (t >> 2) * 64 + w_row(t & 3, i);
       woff[t] = XBYTES + rw * 64 + ((q ^ swz_w64<F32OUT>(rw)) << 4);
     }
   }
