@@ -939,7 +939,10 @@ def check_loss():
 def check_input_pipeline():
     """pvrl_frames_u8_patchify (normalise + bilinear rescale + crop + flip + im2col on decoded uint8 clips) against
     (a) the REFERENCE's own CPU chain (tests/golden/input_pipeline.pt) and (b) the oracle on a ragged random batch.
-    Output is bf16: 1 bf16 ulp (2^-8 relative) on the few values whose fp32 result sits on a rounding boundary."""
+    Output is bf16: 1 bf16 ulp (2^-8 relative) on the few values whose fp32 result sits on a rounding boundary.
+    These are aggregate bounds against the reference's order of operations.  The per-pixel contract -- every element bit-equal to the
+    kernel-order fp32 model, on every clamp, scale, crop, `_views` arrangement and past the workgroup cap -- is held by
+    tests/input_checks.py (tests/test_input_kernels_gpu.py), which also measures how far that model lies from this reference."""
     import os
     import numpy as np
     from procedurevrl_amd import ops
@@ -953,7 +956,9 @@ def check_input_pipeline():
         d = (got.float().cpu() - ref_b).abs()
         ulp = ref_b.abs().clamp_min(2.0 ** -10) * 2.0 ** -7
         out.append((name + " max err / bf16 ulp", float((d / ulp).max()), 1.01))
-        out.append((name + " fraction not bit-equal", float((d > 0).float().mean()), 2e-2))
+        # twice the worst fraction by which the kernel-order model differs from these references on these very inputs (1.45e-3, fp16
+        # operands; tests/test_input_harness_host.py measures and asserts it); was 2e-2
+        out.append((name + " fraction not bit-equal", float((d > 0).float().mean()), 3e-3))
 
     for i, c in enumerate(gold["cases"]):
         np.random.seed(c["seed"])
