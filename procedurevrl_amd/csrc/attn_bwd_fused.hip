@@ -215,7 +215,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p, int 
   const int HD = p.H * PVRL_HEAD_DIM;
   const int n = lane & 31, g = lane >> 5;
   const bool keywave = wave < nqb;
-  const float c = p.scale * 1.4426950408889634f;
+  const float c = p.scale * LOG2E;
   const unsigned ldsbase = __builtin_amdgcn_readfirstlane(lds_addr(smem));
 
   FbItem cur, nxt;

@@ -34,7 +34,7 @@ __global__ __launch_bounds__(64 * S32_NW) void attn_bwd_s32_kernel(AttnArgs p) {
   const int seq = (int)(item / p.H), h = (int)(item - (long)seq * p.H);
   const int S = p.mp.S, HD = p.H * PVRL_HEAD_DIM;
   const int n = lane & 31, g = lane >> 5;
-  const float c = p.scale * 1.4426950408889634f;
+  const float c = p.scale * LOG2E;
   char* Qi = smem + wave * S32_WAVE_LDS;
   char* Di = Qi + 4096;
   char* Ki = Qi + 8192;

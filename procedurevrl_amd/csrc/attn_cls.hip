@@ -59,7 +59,7 @@ __global__ __launch_bounds__(64 * AC_WAVES) void attn_cls_fwd_kernel(AttnCls p) 
   const SeqRows sr = seq_rows(p.mp, seq);
   float q8[8];
   load8(p.qkv + row_of(sr, 0) * p.ld + h * 64 + 8 * c, q8);
-  const float cl = p.scale * 1.4426950408889634f;
+  const float cl = p.scale * LOG2E;
   float m = -INFINITY, l = 0.f, acc[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) acc[e] = 0.f;

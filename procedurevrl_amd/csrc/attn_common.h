@@ -20,19 +20,10 @@ struct SeqMap {
   long cls_base;
 };
 
-__device__ __forceinline__ long seq_row(const SeqMap& mp, int seq, int j) {
-  if (mp.mode == 0) return (long)seq * mp.S + j;
-  const int b = seq / mp.T, t = seq - b * mp.T;
-  return j == 0 ? mp.cls_base + b : (long)b * (mp.S - 1) * mp.T + (long)(j - 1) * mp.T + t;
-}
-
 constexpr int ATT_MAX_TILES = 13;               // S <= 208
 constexpr int ATT_ROWS = ATT_MAX_TILES * 16;    // 208
-constexpr int ATT_ROWS_PAD = 224;               // rounded to 32 for the K=32 MFMA steps
 constexpr int ATT_ROWS_LONG = 26 * 16;          // 416: the long-sequence instantiations of the same kernels (NKT = 17, 26)
 static_assert(ATT_ROWS_LONG == PVRL_ATTN_MAX_S, "include/pvrl.h states the limit the callers read");
-constexpr int ATT_RM_BYTES = ATT_ROWS_PAD * 128;  // row-major [224][64] bf16 tile, 28 KiB
-constexpr int ATT_BL_BYTES = ATT_ROWS_PAD * 128;  // blocked [56][4][4][16] bf16 tile, 28 KiB
 
 // row-major [rows][64] bf16 tile with 16-byte chunk swizzle (conflict-free ds_read_b128 fragments)
 __device__ __forceinline__ int rm_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
@@ -85,33 +76,18 @@ __device__ __forceinline__ SeqRows seq_rows(const SeqMap& mp, int seq) {
 }
 __device__ __forceinline__ long row_of(const SeqRows& r, int j) { return j == 0 ? r.base0 : r.base1 + (long)(j - 1) * r.stride; }
 
-// Cooperative load of one head slice [S rows][64] of a packed activation into LDS (256 threads).
-// All global loads of the tile are issued before the first LDS store so their latencies overlap
-// (7 x 16 B in flight per thread for S = 197).  `src0` (optional) overrides the source row of token 0
-// (side buffer of the per-(b,t) cls rows).  rm / bl may each be null.  Rows >= S are zero-filled.
-constexpr int ATT_LOAD_ITERS = (ATT_ROWS_PAD * 8) / 256;   // 7
-__device__ __forceinline__ void load_head_tile(const op_t* base, long ld, int col0, const SeqRows& sr, int S,
-                                               const op_t* src0, char* rm, int rm_rows, char* bl, int bl_rows,
-                                               int tid) {
-  const int maxrows = rm_rows > bl_rows ? rm_rows : bl_rows;
-  u32x4 v[ATT_LOAD_ITERS];
-#pragma unroll
-  for (int it = 0; it < ATT_LOAD_ITERS; ++it) {
-    const int idx = tid + 256 * it;
-    const int row = idx >> 3, c = idx & 7;
-    v[it] = (u32x4){0u, 0u, 0u, 0u};
-    if (row < S && row < maxrows) {
-      const op_t* src = (row == 0 && src0) ? src0 : base + row_of(sr, row) * ld;
-      v[it] = *reinterpret_cast<const u32x4*>(src + col0 + c * 8);
-    }
-  }
-#pragma unroll
-  for (int it = 0; it < ATT_LOAD_ITERS; ++it) {
-    const int idx = tid + 256 * it;
-    const int row = idx >> 3, c = idx & 7;
-    if (rm && row < rm_rows) *reinterpret_cast<u32x4*>(rm + rm_off(row, c)) = v[it];
-    if (bl && row < bl_rows) *reinterpret_cast<u32x4*>(bl + bl_off(row, c * 8)) = v[it];
-  }
+// 16-byte chunk `c` (of 8) of row `row` of one head slice [S rows][64] of a packed activation, zeros for rows >= S.  `src0` (optional)
+// overrides the source row of token 0 (side buffer of the per-(b,t) cls rows).
+// BRANCH-FREE: every lane loads (rows past the sequence re-read its last row) and the padding is zeroed by a select.  A load
+// inside `if (row < S)` is followed by s_waitcnt vmcnt(0) at the join: the two guarded iterations of
+// a whole-slice load cost the workgroup two extra serial memory round trips in front of its first barrier.
+__device__ __forceinline__ u32x4 chunk_load(const op_t* base, long ld, int col0, const SeqRows& sr, int S, const op_t* src0, int row,
+                                            int c) {
+  const int rc = min(row, S - 1);
+  const op_t* src = (rc == 0 && src0) ? src0 : base + row_of(sr, rc) * ld;
+  const u32x4 v = *reinterpret_cast<const u32x4*>(src + col0 + c * 8);
+  const unsigned keep = row < S ? 0xffffffffu : 0u;
+  return v & (u32x4){keep, keep, keep, keep};
 }
 
 // kernel arguments shared by attn_mfma.hip (forward, two-pass backward) and attn_bwd_fused.hip
@@ -131,6 +107,28 @@ struct AttnArgs {
   op_t* dqkv; op_t* dqkv_cls; long ldd;   // dqkv_cls: [nseq][3*H*64] partial rows for token 0 (mode 1)
 };
 
+// host: AttnArgs from the C arguments of an entry point (include/pvrl.h).  attn_args takes a forward's arguments and leaves the
+// backward fields zero; attn_args_bwd takes a backward's (`o` is then the forward's output, `dvec` the D buffer or workspace).
+inline AttnArgs attn_args(const void* qkv, int64_t ld, int64_t nseq, int64_t S, int64_t H, int mode, int64_t T, int64_t cls_base,
+                          float scale, int causal, const void* key_padding_mask, void* o, void* o_cls, int64_t ldo, float* lse) {
+  AttnArgs p = {};
+  p.qkv = (const op_t*)qkv; p.ld = ld; p.H = (int)H; p.nseq = (int)nseq;
+  p.mp.mode = mode; p.mp.S = (int)S; p.mp.T = (int)T; p.mp.cls_base = cls_base;
+  p.scale = scale; p.causal = causal; p.kpm = (const unsigned char*)key_padding_mask;
+  p.o = (op_t*)o; p.o_cls = (op_t*)o_cls; p.ldo = ldo; p.lse = lse;
+  return p;
+}
+inline AttnArgs attn_args_bwd(const void* qkv, int64_t ld, int64_t nseq, int64_t S, int64_t H, int mode, int64_t T, int64_t cls_base,
+                              float scale, int causal, const void* key_padding_mask, const void* o, const void* o_cls,
+                              const void* d_o, const void* d_o_cls, int64_t ldo, const float* lse, float* dvec, void* dqkv,
+                              void* dqkv_cls, int64_t ldd) {
+  AttnArgs p = attn_args(qkv, ld, nseq, S, H, mode, T, cls_base, scale, causal, key_padding_mask, nullptr, nullptr, ldo,
+                         const_cast<float*>(lse));
+  p.ofw = (const op_t*)o; p.ofw_cls = (const op_t*)o_cls; p.d_o = (const op_t*)d_o; p.d_o_cls = (const op_t*)d_o_cls;
+  p.dvec = dvec; p.dqkv = (op_t*)dqkv; p.dqkv_cls = (op_t*)dqkv_cls; p.ldd = ldd;
+  return p;
+}
+
 // row pointer helpers for per-token outputs / inputs that keep token 0 in a side buffer (mode 1)
 template <typename T>
 __device__ __forceinline__ T* tok_ptr(T* tok, T* cls, long ld, const SeqMap& mp, const SeqRows& sr, int seq, int j) {
@@ -142,6 +140,70 @@ __device__ __forceinline__ unsigned pack_opx2(float a, float b) {
   union { opx2 v; unsigned u; } x;
   x.v[0] = (op_t)a; x.v[1] = (op_t)b;
   return x.u;
+}
+
+// ---- lane-level pieces of the head_dim-64 kernels (attn_mfma.hip, attn_long.hip).  MFMA operands are "swapped" (a = rows read from a
+// blocked LDS image, b = the wave's own rows), so lane (i = lane & 15, q4 = lane >> 4) owns ONE row of the wave's tile -- a query in
+// the forward and dQ, a key in dK / dV -- and elements 4 q4 .. 4 q4 + 3 of each 16 along the other dimension.
+constexpr float LOG2E = 1.4426950408889634f;
+
+// the wave's own fragments of a row: 8 columns at p (= row + 8 q4) and 8 at p + 32, the b-operands of the two K = 32 steps over head_dim
+__device__ __forceinline__ void row_frags(const op_t* p, opx8& f0, opx8& f1) {
+  f0 = *reinterpret_cast<const opx8*>(p);
+  f1 = *reinterpret_cast<const opx8*>(p + 32);
+}
+
+// maximum / sum over the four lanes (q4 = 0..3) that share a row
+__device__ __forceinline__ float q4_max(float v) {
+  v = fmaxf(v, __shfl_xor(v, 16, 64));
+  return fmaxf(v, __shfl_xor(v, 32, 64));
+}
+__device__ __forceinline__ float q4_sum(float v) {
+  v += __shfl_xor(v, 16, 64);
+  return v + __shfl_xor(v, 32, 64);
+}
+
+// S and dP of one 16-row tile of the blocked images A and B (a-operands; `row` = the tile's first row + i) against the wave's own
+// fragments x and y (b-operands): s[r] = A[tile row 4 q4 + r] . x[the lane's row], dp[r] = B[same row] . y[the lane's row].
+// Statement order as it stood in the kernels: four fragment reads, then the four products.
+__device__ __forceinline__ void s_dp_tile(const char* A, const char* B, int row, int q4, opx8 x0, opx8 x1, opx8 y0, opx8 y1, f32x4& s,
+                                          f32x4& dp) {
+  const opx8 a0 = bl_row_frag(A, row, q4);
+  const opx8 a1 = bl_row_frag(A, row, 4 + q4);
+  const opx8 b0 = bl_row_frag(B, row, q4);
+  const opx8 b1 = bl_row_frag(B, row, 4 + q4);
+  s = (f32x4){0.f, 0.f, 0.f, 0.f};
+  s = MFMA_16x16x32(a0, x0, s, 0, 0, 0);
+  s = MFMA_16x16x32(a1, x1, s, 0, 0, 0);
+  dp = (f32x4){0.f, 0.f, 0.f, 0.f};
+  dp = MFMA_16x16x32(b0, y0, dp, 0, 0, 0);
+  dp = MFMA_16x16x32(b1, y1, dp, 0, 0, 0);
+}
+
+// P recomputed from the saved statistics, and dS = P * (dP - D) * scale: c = scale * log2(e), lse2 = lse * log2(e), dss = D * scale
+__device__ __forceinline__ float p_from_lse(float s, float c, float lse2) { return __builtin_amdgcn_exp2f(fmaf(s, c, -lse2)); }
+__device__ __forceinline__ float ds_of(float pr, float dp, float scale, float dss) { return pr * fmaf(dp, scale, -dss); }
+
+// the lane's 16 accumulator values of an output row (columns 16 dt + 4 q4 + r), times `mul`, as four 8-byte stores; op = row + 4 q4
+__device__ __forceinline__ void store_acc(op_t* op, const f32x4 (&acc)[4], float mul = 1.f) {
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) {
+    opx4 ov;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) ov[r] = (op_t)(acc[dt][r] * mul);
+    *reinterpret_cast<opx4*>(op + 16 * dt) = ov;
+  }
+}
+// two accumulators (dK and dV), their stores interleaved
+__device__ __forceinline__ void store_acc2(op_t* op0, const f32x4 (&acc0)[4], op_t* op1, const f32x4 (&acc1)[4]) {
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) {
+    opx4 o0, o1;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { o0[r] = (op_t)acc0[dt][r]; o1[r] = (op_t)acc1[dt][r]; }
+    *reinterpret_cast<opx4*>(op0 + 16 * dt) = o0;
+    *reinterpret_cast<opx4*>(op1 + 16 * dt) = o1;
+  }
 }
 
 // ---- head_dim 96 (MViTv2): 32-row tiles of 6 sixteen-column blocks, shared by attn_pool.hip and mvit_rel.hip

@@ -27,20 +27,10 @@ constexpr int QT = PVRL_ATTN_LONG_QT;    // rows a workgroup owns
 constexpr int NW = QT / 16;              // waves per workgroup
 constexpr int NT = 64 * NW;
 constexpr int TILE = KT * 128;           // bytes of one blocked [KT][64] tile
-constexpr float LOG2E = 1.4426950408889634f;
 static_assert(KT == 64 && KT * 8 == NT, "one 16-byte chunk per thread and tile; the tile loops below are written for 4 sub-tiles of 16 rows");
 
-// this thread's 16-byte chunk of rows [r0, r0 + KT) of a head slice.  Branch-free: rows past the sequence re-read its last row and
-// come out as zeros (attn_mfma.hip, tile_issue).  `src0` (optional) overrides the source row of token 0.
-__device__ __forceinline__ u32x4 chunk_load(const op_t* base, long ld, int col0, const SeqRows& sr, int S, const op_t* src0, int r0,
-                                            int tid) {
-  const int row = r0 + (tid >> 3), c = tid & 7;
-  const int rc = min(row, S - 1);
-  const op_t* src = (rc == 0 && src0) ? src0 : base + row_of(sr, rc) * ld;
-  const u32x4 v = *reinterpret_cast<const u32x4*>(src + col0 + c * 8);
-  const unsigned keep = row < S ? 0xffffffffu : 0u;
-  return v & (u32x4){keep, keep, keep, keep};
-}
+// A streamed tile is one 16-byte chunk per thread: chunk_load (attn_common.h) of row r0 + (tid >> 3), chunk tid & 7, put into the
+// blocked image by chunk_store.
 __device__ __forceinline__ void chunk_store(char* tile, const u32x4& v, int tid) {
   *reinterpret_cast<u32x4*>(tile + bl_off(tid >> 3, (tid & 7) * 8)) = v;
 }
@@ -58,29 +48,38 @@ __device__ __forceinline__ Item item_of(const AttnArgs& p, int nblk) {
   return it;
 }
 
+// What the three kernels know before they touch data: tid / lane / wave (wave-uniform), S, HD = H * 64 (the column distance
+// q -> k -> v), the workgroup's (seq, h) and the sequence's rows sr, the lane's place in a 16 x 16 tile (q4, i), its own row ROW
+// (a query in the forward and dQ, a key in dK / dV), the number NTILES of streamed tiles, c = scale * log2(e), and this thread's
+// chunk of a streamed tile (row crow, 16-byte chunk cc).  `live` is wave-uniform: a wave past the sequence still loads and meets
+// the barriers.  (A macro for the reason given in attn_mfma.hip, ATTN_WG_PROLOGUE.)
+#define ATTN_LONG_PROLOGUE(p, ROW, NTILES)                          \
+  const int tid = threadIdx.x, lane = tid & 63;                     \
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);        \
+  const int S = p.mp.S, HD = p.H * PVRL_HEAD_DIM;                   \
+  const Item it = item_of(p, (S + QT - 1) / QT);                    \
+  const int seq = it.seq, h = it.h;                                 \
+  const SeqRows sr = seq_rows(p.mp, seq);                           \
+  const int q4 = lane >> 4, i = lane & 15;                          \
+  const int row0 = it.blk * QT + wave * 16;                         \
+  const int ROW = row0 + i;                                         \
+  const bool live = row0 < S;                                       \
+  const int NTILES = (S + KT - 1) / KT;                             \
+  const float c = p.scale * LOG2E;                                  \
+  const int crow = tid >> 3, cc = tid & 7
+
 // ------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(NT, 2) void attn_long_fwd_kernel(AttnArgs p) {
   __shared__ __attribute__((aligned(16))) char smem[4 * TILE];   // [buffer][K | V]
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int S = p.mp.S, HD = p.H * PVRL_HEAD_DIM;
-  const Item it = item_of(p, (S + QT - 1) / QT);
-  const int seq = it.seq, h = it.h;
-  const SeqRows sr = seq_rows(p.mp, seq);
-  const int q4 = lane >> 4, i = lane & 15;
-  const int q0 = it.blk * QT + wave * 16;
-  const int query = q0 + i;
-  const bool live = q0 < S;              // wave-uniform: a wave past the sequence still loads and meets the barriers
-  const int nkt = (S + KT - 1) / KT;
-  const float c = p.scale * LOG2E;
+  ATTN_LONG_PROLOGUE(p, query, nkt);
 
   const op_t* qp = p.qkv + row_of(sr, min(query, S - 1)) * p.ld + h * 64 + q4 * 8;
-  const opx8 qf0 = *reinterpret_cast<const opx8*>(qp);
-  const opx8 qf1 = *reinterpret_cast<const opx8*>(qp + 32);
-  u32x4 kr = chunk_load(p.qkv, p.ld, HD + h * 64, sr, S, nullptr, 0, tid);
-  u32x4 vr = chunk_load(p.qkv, p.ld, 2 * HD + h * 64, sr, S, nullptr, 0, tid);
+  opx8 qf0, qf1;
+  row_frags(qp, qf0, qf1);
+  u32x4 kr = chunk_load(p.qkv, p.ld, HD + h * 64, sr, S, nullptr, crow, cc);
+  u32x4 vr = chunk_load(p.qkv, p.ld, 2 * HD + h * 64, sr, S, nullptr, crow, cc);
   chunk_store(smem, kr, tid);
   chunk_store(smem + TILE, vr, tid);
   __syncthreads();
@@ -95,8 +94,8 @@ __global__ __launch_bounds__(NT, 2) void attn_long_fwd_kernel(AttnArgs p) {
     const char* Vb = Kb + TILE;
     char* nxt = smem + ((kt + 1) & 1) * 2 * TILE;
     // the next tile's loads fly under this tile's math (past the last tile: clamped rows, zeros, never read)
-    kr = chunk_load(p.qkv, p.ld, HD + h * 64, sr, S, nullptr, (kt + 1) * KT, tid);
-    vr = chunk_load(p.qkv, p.ld, 2 * HD + h * 64, sr, S, nullptr, (kt + 1) * KT, tid);
+    kr = chunk_load(p.qkv, p.ld, HD + h * 64, sr, S, nullptr, (kt + 1) * KT + crow, cc);
+    vr = chunk_load(p.qkv, p.ld, 2 * HD + h * 64, sr, S, nullptr, (kt + 1) * KT + crow, cc);
     if (live) {
       f32x4 sc[4];
 #pragma unroll
@@ -119,8 +118,7 @@ __global__ __launch_bounds__(NT, 2) void attn_long_fwd_kernel(AttnArgs p) {
           sc[j][r] = t;
           tmax = fmaxf(tmax, t);
         }
-      tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
-      tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+      tmax = q4_max(tmax);
       const float mn = fmaxf(m, tmax);
       const float alpha = __builtin_amdgcn_exp2f(m - mn);
       float psum = 0.f;
@@ -132,8 +130,7 @@ __global__ __launch_bounds__(NT, 2) void attn_long_fwd_kernel(AttnArgs p) {
           sc[j][r] = e;
           psum += e;
         }
-      psum += __shfl_xor(psum, 16, 64);
-      psum += __shfl_xor(psum, 32, 64);
+      psum = q4_sum(psum);
       l = fmaf(l, alpha, psum);
       m = mn;
 #pragma unroll
@@ -161,6 +158,7 @@ __global__ __launch_bounds__(NT, 2) void attn_long_fwd_kernel(AttnArgs p) {
   if (query < S) {
     const float inv = l > 0.f ? 1.0f / l : 0.f;
     op_t* op = tok_ptr(p.o, p.o_cls, p.ldo, p.mp, sr, seq, query) + h * 64 + 4 * q4;
+    // (spelt out, not store_acc: through the helper the compiler orders this kernel's instructions differently)
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
       opx4 ov;
@@ -177,38 +175,26 @@ __global__ __launch_bounds__(NT, 2) void attn_long_fwd_kernel(AttnArgs p) {
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(NT, 2) void attn_long_bwd_q_kernel(AttnArgs p) {
   __shared__ __attribute__((aligned(16))) char smem[4 * TILE];   // [buffer][K | V]
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int S = p.mp.S, HD = p.H * PVRL_HEAD_DIM;
-  const Item it = item_of(p, (S + QT - 1) / QT);
-  const int seq = it.seq, h = it.h;
-  const SeqRows sr = seq_rows(p.mp, seq);
-  const int q4 = lane >> 4, i = lane & 15;
-  const int q0 = it.blk * QT + wave * 16;
-  const int query = q0 + i;
+  ATTN_LONG_PROLOGUE(p, query, nkt);
   const int qj = min(query, S - 1);
-  const bool live = q0 < S;
-  const int nkt = (S + KT - 1) / KT;
-  const float c = p.scale * LOG2E;
 
   const op_t* qp = p.qkv + row_of(sr, qj) * p.ld + h * 64 + q4 * 8;
-  const opx8 qf0 = *reinterpret_cast<const opx8*>(qp);
-  const opx8 qf1 = *reinterpret_cast<const opx8*>(qp + 32);
+  opx8 qf0, qf1;
+  row_frags(qp, qf0, qf1);
   const op_t* dop = tok_ptr(p.d_o, p.d_o_cls, p.ldo, p.mp, sr, seq, qj) + h * 64 + q4 * 8;
-  const opx8 df0 = *reinterpret_cast<const opx8*>(dop);
-  const opx8 df1 = *reinterpret_cast<const opx8*>(dop + 32);
+  opx8 df0, df1;
+  row_frags(dop, df0, df1);
   const op_t* ofp = tok_ptr(p.ofw, p.ofw_cls, p.ldo, p.mp, sr, seq, qj) + h * 64 + q4 * 8;
-  const opx8 of0 = *reinterpret_cast<const opx8*>(ofp);
-  const opx8 of1 = *reinterpret_cast<const opx8*>(ofp + 32);
+  opx8 of0, of1;
+  row_frags(ofp, of0, of1);
   const long stat = ((long)seq * p.H + h) * S;
   const float lse2 = p.lse[stat + qj] * LOG2E;
-  u32x4 kr = chunk_load(p.qkv, p.ld, HD + h * 64, sr, S, nullptr, 0, tid);
-  u32x4 vr = chunk_load(p.qkv, p.ld, 2 * HD + h * 64, sr, S, nullptr, 0, tid);
+  u32x4 kr = chunk_load(p.qkv, p.ld, HD + h * 64, sr, S, nullptr, crow, cc);
+  u32x4 vr = chunk_load(p.qkv, p.ld, 2 * HD + h * 64, sr, S, nullptr, crow, cc);
   float dsum = 0.f;
 #pragma unroll
   for (int e = 0; e < 8; ++e) dsum += (float)df0[e] * (float)of0[e] + (float)df1[e] * (float)of1[e];
-  dsum += __shfl_xor(dsum, 16, 64);
-  dsum += __shfl_xor(dsum, 32, 64);
+  dsum = q4_sum(dsum);
   const float dss = dsum * p.scale;
   if (q4 == 0 && query < S) p.dvec[stat + query] = dsum;
   chunk_store(smem, kr, tid);
@@ -223,8 +209,8 @@ __global__ __launch_bounds__(NT, 2) void attn_long_bwd_q_kernel(AttnArgs p) {
     const char* Kb = smem + (kt & 1) * 2 * TILE;
     const char* Vb = Kb + TILE;
     char* nxt = smem + ((kt + 1) & 1) * 2 * TILE;
-    kr = chunk_load(p.qkv, p.ld, HD + h * 64, sr, S, nullptr, (kt + 1) * KT, tid);
-    vr = chunk_load(p.qkv, p.ld, 2 * HD + h * 64, sr, S, nullptr, (kt + 1) * KT, tid);
+    kr = chunk_load(p.qkv, p.ld, HD + h * 64, sr, S, nullptr, (kt + 1) * KT + crow, cc);
+    vr = chunk_load(p.qkv, p.ld, 2 * HD + h * 64, sr, S, nullptr, (kt + 1) * KT + crow, cc);
     if (live) {
       const int kbase = kt * KT;
       const bool ragged = kbase + KT > S;
@@ -233,22 +219,13 @@ __global__ __launch_bounds__(NT, 2) void attn_long_bwd_q_kernel(AttnArgs p) {
         opx8 sf;
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
-          const int krow = (2 * ks2 + half) * 16 + i;
-          const opx8 k0 = bl_row_frag(Kb, krow, q4);
-          const opx8 k1 = bl_row_frag(Kb, krow, 4 + q4);
-          const opx8 v0 = bl_row_frag(Vb, krow, q4);
-          const opx8 v1 = bl_row_frag(Vb, krow, 4 + q4);
-          f32x4 s = (f32x4){0.f, 0.f, 0.f, 0.f};
-          s = MFMA_16x16x32(k0, qf0, s, 0, 0, 0);
-          s = MFMA_16x16x32(k1, qf1, s, 0, 0, 0);
-          f32x4 dp = (f32x4){0.f, 0.f, 0.f, 0.f};
-          dp = MFMA_16x16x32(v0, df0, dp, 0, 0, 0);
-          dp = MFMA_16x16x32(v1, df1, dp, 0, 0, 0);
+          f32x4 s, dp;
+          s_dp_tile(Kb, Vb, (2 * ks2 + half) * 16 + i, q4, qf0, qf1, df0, df1, s, dp);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            float pr = __builtin_amdgcn_exp2f(fmaf(s[r], c, -lse2));
+            float pr = p_from_lse(s[r], c, lse2);
             if (ragged && kbase + (2 * ks2 + half) * 16 + 4 * q4 + r >= S) pr = 0.f;
-            sf[4 * half + r] = (op_t)(pr * fmaf(dp[r], p.scale, -dss));
+            sf[4 * half + r] = (op_t)ds_of(pr, dp[r], p.scale, dss);
           }
         }
 #pragma unroll
@@ -265,13 +242,7 @@ __global__ __launch_bounds__(NT, 2) void attn_long_bwd_q_kernel(AttnArgs p) {
 
   if (query < S) {
     op_t* op = tok_ptr(p.dqkv, p.dqkv_cls, p.ldd, p.mp, sr, seq, query) + h * 64 + 4 * q4;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      opx4 ov;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) ov[r] = (op_t)dq[dt][r];
-      *reinterpret_cast<opx4*>(op + 16 * dt) = ov;
-    }
+    store_acc(op, dq);
   }
 }
 
@@ -281,26 +252,14 @@ __global__ __launch_bounds__(NT, 2) void attn_long_bwd_q_kernel(AttnArgs p) {
 __global__ __launch_bounds__(NT, 2) void attn_long_bwd_kv_kernel(AttnArgs p) {
   __shared__ __attribute__((aligned(16))) char smem[4 * TILE + 4 * KT * 4];   // [buffer][Q | dO], then [buffer][lse | D]
   float* stats = reinterpret_cast<float*>(smem + 4 * TILE);
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int S = p.mp.S, HD = p.H * PVRL_HEAD_DIM;
-  const Item it = item_of(p, (S + QT - 1) / QT);
-  const int seq = it.seq, h = it.h;
-  const SeqRows sr = seq_rows(p.mp, seq);
-  const int q4 = lane >> 4, i = lane & 15;
-  const int k0r = it.blk * QT + wave * 16;
-  const int key = k0r + i;
-  const bool live = k0r < S;
-  const int nqt = (S + KT - 1) / KT;
-  const float c = p.scale * LOG2E;
+  ATTN_LONG_PROLOGUE(p, key, nqt);
   const long stat = ((long)seq * p.H + h) * S;
   const op_t* src0 = p.mp.mode == 1 ? p.d_o_cls + (long)seq * p.ldo : nullptr;   // dO of token 0 lives in the side buffer
 
   const op_t* kp = p.qkv + row_of(sr, min(key, S - 1)) * p.ld + HD + h * 64 + q4 * 8;
-  const opx8 kf0 = *reinterpret_cast<const opx8*>(kp);
-  const opx8 kf1 = *reinterpret_cast<const opx8*>(kp + 32);
-  const opx8 vf0 = *reinterpret_cast<const opx8*>(kp + HD);
-  const opx8 vf1 = *reinterpret_cast<const opx8*>(kp + HD + 32);
+  opx8 kf0, kf1, vf0, vf1;
+  row_frags(kp, kf0, kf1);
+  row_frags(kp + HD, vf0, vf1);
 
   // threads 0..63 carry lse * log2(e), threads 64..127 D * scale of the tile's 64 queries (zeros past the sequence)
   const int srow = tid & 63;
@@ -311,8 +270,8 @@ __global__ __launch_bounds__(NT, 2) void attn_long_bwd_kv_kernel(AttnArgs p) {
     const float v = is_lse ? p.lse[idx] * LOG2E : p.dvec[idx] * p.scale;
     return q < S ? v : 0.f;
   };
-  u32x4 qr = chunk_load(p.qkv, p.ld, h * 64, sr, S, nullptr, 0, tid);
-  u32x4 dr = chunk_load(p.d_o, p.ldo, h * 64, sr, S, src0, 0, tid);
+  u32x4 qr = chunk_load(p.qkv, p.ld, h * 64, sr, S, nullptr, crow, cc);
+  u32x4 dr = chunk_load(p.d_o, p.ldo, h * 64, sr, S, src0, crow, cc);
   float st = has_stat ? stat_load(0) : 0.f;
   chunk_store(smem, qr, tid);
   chunk_store(smem + TILE, dr, tid);
@@ -329,8 +288,8 @@ __global__ __launch_bounds__(NT, 2) void attn_long_bwd_kv_kernel(AttnArgs p) {
     const float* lse_s = stats + (qt & 1) * 2 * KT;
     const float* dv_s = lse_s + KT;
     char* nxt = smem + ((qt + 1) & 1) * 2 * TILE;
-    qr = chunk_load(p.qkv, p.ld, h * 64, sr, S, nullptr, (qt + 1) * KT, tid);
-    dr = chunk_load(p.d_o, p.ldo, h * 64, sr, S, src0, (qt + 1) * KT, tid);
+    qr = chunk_load(p.qkv, p.ld, h * 64, sr, S, nullptr, (qt + 1) * KT + crow, cc);
+    dr = chunk_load(p.d_o, p.ldo, h * 64, sr, S, src0, (qt + 1) * KT + crow, cc);
     st = has_stat ? stat_load((qt + 1) * KT) : 0.f;
     if (live) {
       const int qbase = qt * KT;
@@ -340,27 +299,18 @@ __global__ __launch_bounds__(NT, 2) void attn_long_bwd_kv_kernel(AttnArgs p) {
         opx8 pf, sf;
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
-          const int qrow = (2 * u + half) * 16 + i;   // a-operand row: query
-          const opx8 a0 = bl_row_frag(Qb, qrow, q4);
-          const opx8 a1 = bl_row_frag(Qb, qrow, 4 + q4);
-          const opx8 d0 = bl_row_frag(Db, qrow, q4);
-          const opx8 d1 = bl_row_frag(Db, qrow, 4 + q4);
-          f32x4 s = (f32x4){0.f, 0.f, 0.f, 0.f};
-          s = MFMA_16x16x32(a0, kf0, s, 0, 0, 0);
-          s = MFMA_16x16x32(a1, kf1, s, 0, 0, 0);
-          f32x4 dp = (f32x4){0.f, 0.f, 0.f, 0.f};
-          dp = MFMA_16x16x32(d0, vf0, dp, 0, 0, 0);
-          dp = MFMA_16x16x32(d1, vf1, dp, 0, 0, 0);
+          f32x4 s, dp;
+          s_dp_tile(Qb, Db, (2 * u + half) * 16 + i, q4, kf0, kf1, vf0, vf1, s, dp);   // a-operand rows: queries
           // s[r] = S[query = qbase + (2u + half) * 16 + 4 * q4 + r][key]
           const int qb = (2 * u + half) * 16 + 4 * q4;
           const f32x4 l4 = *reinterpret_cast<const f32x4*>(lse_s + qb);   // lse * log2(e)
           const f32x4 d4 = *reinterpret_cast<const f32x4*>(dv_s + qb);    // D * scale
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            float pr = __builtin_amdgcn_exp2f(fmaf(s[r], c, -l4[r]));
+            float pr = p_from_lse(s[r], c, l4[r]);
             if (ragged && qbase + qb + r >= S) pr = 0.f;
             pf[half * 4 + r] = (op_t)pr;
-            sf[half * 4 + r] = (op_t)(pr * fmaf(dp[r], p.scale, -d4[r]));
+            sf[half * 4 + r] = (op_t)ds_of(pr, dp[r], p.scale, d4[r]);
           }
         }
 #pragma unroll
@@ -380,14 +330,7 @@ __global__ __launch_bounds__(NT, 2) void attn_long_bwd_kv_kernel(AttnArgs p) {
 
   if (key < S) {
     op_t* op = tok_ptr(p.dqkv, p.dqkv_cls, p.ldd, p.mp, sr, seq, key) + HD + h * 64 + 4 * q4;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      opx4 ok, ov;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { ok[r] = (op_t)dk[dt][r]; ov[r] = (op_t)dv[dt][r]; }
-      *reinterpret_cast<opx4*>(op + 16 * dt) = ok;
-      *reinterpret_cast<opx4*>(op + HD + 16 * dt) = ov;
-    }
+    store_acc2(op, dk, op + HD, dv);
   }
 }
 
@@ -407,11 +350,7 @@ extern "C" int pvrl_attn_long_fwd(const void* qkv, int64_t ld, int64_t nseq, int
                                   int64_t cls_base, float scale, void* o, void* o_cls, int64_t ldo, float* lse, void* stream) {
   if (nseq < 0 || nseq > 0x7fffffffL || S < 1 || S > PVRL_ATTN_LONG_MAX_S || H <= 0 || H > 0x7fffffffL || T > 0x7fffffffL)
     return PVRL_EINVAL;
-  AttnArgs p = {};
-  p.qkv = (const op_t*)qkv; p.ld = ld; p.H = (int)H; p.nseq = (int)nseq;
-  p.mp.mode = mode; p.mp.S = (int)S; p.mp.T = (int)T; p.mp.cls_base = cls_base;
-  p.scale = scale;
-  p.o = (op_t*)o; p.o_cls = (op_t*)o_cls; p.ldo = ldo; p.lse = lse;
+  const AttnArgs p = attn_args(qkv, ld, nseq, S, H, mode, T, cls_base, scale, 0, nullptr, o, o_cls, ldo, lse);
   if (nseq == 0) return PVRL_OK;
   long grid = 0;
   if (int e = check_long(p, &grid)) return e;
@@ -432,13 +371,8 @@ extern "C" int pvrl_attn_long_bwd(const void* qkv, int64_t ld, int64_t nseq, int
                                   void* workspace, int64_t workspace_bytes, void* stream) {
   if (nseq < 0 || nseq > 0x7fffffffL || S < 1 || S > PVRL_ATTN_LONG_MAX_S || H <= 0 || H > 0x7fffffffL || T > 0x7fffffffL)
     return PVRL_EINVAL;
-  AttnArgs p = {};
-  p.qkv = (const op_t*)qkv; p.ld = ld; p.H = (int)H; p.nseq = (int)nseq;
-  p.mp.mode = mode; p.mp.S = (int)S; p.mp.T = (int)T; p.mp.cls_base = cls_base;
-  p.scale = scale;
-  p.ofw = (const op_t*)o; p.ofw_cls = (const op_t*)o_cls; p.d_o = (const op_t*)d_o; p.d_o_cls = (const op_t*)d_o_cls;
-  p.ldo = ldo; p.lse = const_cast<float*>(lse); p.dvec = (float*)workspace;
-  p.dqkv = (op_t*)dqkv; p.dqkv_cls = (op_t*)dqkv_cls; p.ldd = ldd;
+  const AttnArgs p = attn_args_bwd(qkv, ld, nseq, S, H, mode, T, cls_base, scale, 0, nullptr, o, o_cls, d_o, d_o_cls, ldo, lse,
+                                   (float*)workspace, dqkv, dqkv_cls, ldd);
   if (nseq == 0) return PVRL_OK;
   long grid = 0;
   if (int e = check_long(p, &grid)) return e;

@@ -56,38 +56,50 @@ __device__ __forceinline__ unsigned long long pad_bits_q(const AttnArgs& p, int 
 
 // Cooperative load of one head slice [S rows][64] of a packed activation into the blocked LDS image, in two halves so a
 // kernel can put EVERY global load it needs (both tiles + its waves' own fragments) in flight before the first wait.
-template <int NT, int ROWS = ATT_ROWS_PAD>
+// The image has ROWS rows (a multiple of 32, for the K = 32 MFMA steps), the workgroup NT threads; chunk_load (attn_common.h) is
+// branch-free, so an issue is nothing but loads.
+template <int NT, int ROWS>
 struct TileRegs { u32x4 v[(ROWS * 8 + NT - 1) / NT]; };
 
-template <int NT, int ROWS = ATT_ROWS_PAD>
+template <int NT, int ROWS>
 __device__ __forceinline__ void tile_issue(TileRegs<NT, ROWS>& t, const op_t* base, long ld, int col0, const SeqRows& sr, int S,
-                                           const op_t* src0, int rows, int tid) {
+                                           const op_t* src0, int tid) {
+  constexpr int ITERS = (ROWS * 8 + NT - 1) / NT;
+#pragma unroll
+  for (int it = 0; it < ITERS; ++it) {
+    const int idx = tid + NT * it;
+    t.v[it] = chunk_load(base, ld, col0, sr, S, src0, idx >> 3, idx & 7);
+  }
+}
+template <int NT, int ROWS>
+__device__ __forceinline__ void tile_commit(const TileRegs<NT, ROWS>& t, char* bl, int tid) {
   constexpr int ITERS = (ROWS * 8 + NT - 1) / NT;
 #pragma unroll
   for (int it = 0; it < ITERS; ++it) {
     const int idx = tid + NT * it;
     const int row = idx >> 3, c = idx & 7;
-    // BRANCH-FREE: every lane loads (rows past the sequence re-read its last row) and the padding is zeroed by a select.  A load
-    // inside `if (row < S)` is followed by s_waitcnt vmcnt(0) at the join: the two guarded iterations of
-    // this loop cost the workgroup two extra serial memory round trips in front of its first barrier.
-    const int rc = min(row, S - 1);
-    const op_t* src = (rc == 0 && src0) ? src0 : base + row_of(sr, rc) * ld;
-    const u32x4 v = *reinterpret_cast<const u32x4*>(src + col0 + c * 8);
-    const unsigned keep = row < S ? 0xffffffffu : 0u;
-    t.v[it] = v & (u32x4){keep, keep, keep, keep};
-    (void)rows;
+    if (row < ROWS) *reinterpret_cast<u32x4*>(bl + bl_off(row, c * 8)) = t.v[it];
   }
 }
-template <int NT, int ROWS = ATT_ROWS_PAD>
-__device__ __forceinline__ void tile_commit(const TileRegs<NT, ROWS>& t, char* bl, int rows, int tid) {
-  constexpr int ITERS = (ROWS * 8 + NT - 1) / NT;
-#pragma unroll
-  for (int it = 0; it < ITERS; ++it) {
-    const int idx = tid + NT * it;
-    const int row = idx >> 3, c = idx & 7;
-    if (row < rows) *reinterpret_cast<u32x4*>(bl + bl_off(row, c * 8)) = t.v[it];
-  }
-}
+
+// What every kernel of this file knows about its workgroup and lane before it touches data: tid / lane / wave (wave-uniform),
+// the workgroup's (seq, h), S (SC: the sequence length as a compile-time constant, 0 = run time), HD = H * 64 (the column
+// distance q -> k -> v), the sequence's rows sr, and the lane's place in a 16 x 16 tile (q4, i).  A workgroup past the last
+// sequence (the grid is rounded up to 8 sequences) returns.
+// Workgroups are dealt round-robin to the 8 XCDs: keep the H heads of a sequence on ONE XCD, back to back, so the
+// 128-byte head slices of a token row are fetched together (same DRAM pages, same L2).
+// A macro: the same lines as a struct filled by an inline function changed the register counts of 39 of the 48 instantiations
+// (the compiler's early passes run before the inliner and see the struct in memory).
+#define ATTN_WG_PROLOGUE(p, SC)                                            \
+  const int tid = threadIdx.x, lane = tid & 63;                            \
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);               \
+  const int xj = blockIdx.x >> 3;                                          \
+  const int seq = (xj / p.H) * 8 + (blockIdx.x & 7), h = xj % p.H;         \
+  if (seq >= p.nseq) return;                                               \
+  const int S = SC ? SC : p.mp.S;                                          \
+  const int HD = p.H * PVRL_HEAD_DIM;                                      \
+  const SeqRows sr = seq_rows(p.mp, seq);                                  \
+  const int q4 = lane >> 4, i = lane & 15
 
 // ------------------------------------------------------------------------------------------
 // forward
@@ -99,18 +111,8 @@ __global__ __launch_bounds__(64 * NW, NKT > 13 ? 2 : (NW + 1) / 2) void attn_fwd
   __shared__ __attribute__((aligned(16))) char smem[2 * BL];
   char* Kb = smem;
   char* Vb = smem + BL;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // workgroups are dealt round-robin to the 8 XCDs: keep the H heads of a sequence on ONE XCD, back to back, so the
-  // 128-byte head slices of a token row are fetched together (same DRAM pages, same L2)
-  const int xj = blockIdx.x >> 3;
-  const int seq = (xj / p.H) * 8 + (blockIdx.x & 7), h = xj % p.H;
-  if (seq >= p.nseq) return;
-  const int S = SC ? SC : p.mp.S;     // SC: the sequence length as a compile-time constant (0 = run time)
-  const int HD = p.H * PVRL_HEAD_DIM;
-  const SeqRows sr = seq_rows(p.mp, seq);
+  ATTN_WG_PROLOGUE(p, SC);
   constexpr int MAXT = (NKT + NW - 1) / NW;   // query tiles per wave
-  const int q4 = lane >> 4, i = lane & 15;
   const int nqt = (S + 15) >> 4;
   // every global load of the workgroup goes out before the first wait: this wave's query fragments, then K and V
   opx8 qf[MAXT][2];
@@ -119,15 +121,14 @@ __global__ __launch_bounds__(64 * NW, NKT > 13 ? 2 : (NW + 1) / 2) void attn_fwd
     const int query = (wave + t * NW) * 16 + i;
     const int qrow = query < S ? query : S - 1;
     const op_t* qp = p.qkv + row_of(sr, qrow) * p.ld + h * 64 + q4 * 8;
-    qf[t][0] = *reinterpret_cast<const opx8*>(qp);
-    qf[t][1] = *reinterpret_cast<const opx8*>(qp + 32);
+    row_frags(qp, qf[t][0], qf[t][1]);
   }
   {
     TileRegs<64 * NW, NKS2 * 32> kr, vr;
-    tile_issue<64 * NW, NKS2 * 32>(kr, p.qkv, p.ld, HD + h * 64, sr, S, nullptr, NKS2 * 32, tid);
-    tile_issue<64 * NW, NKS2 * 32>(vr, p.qkv, p.ld, 2 * HD + h * 64, sr, S, nullptr, NKS2 * 32, tid);
-    tile_commit<64 * NW, NKS2 * 32>(kr, Kb, NKS2 * 32, tid);
-    tile_commit<64 * NW, NKS2 * 32>(vr, Vb, NKS2 * 32, tid);
+    tile_issue<64 * NW, NKS2 * 32>(kr, p.qkv, p.ld, HD + h * 64, sr, S, nullptr, tid);
+    tile_issue<64 * NW, NKS2 * 32>(vr, p.qkv, p.ld, 2 * HD + h * 64, sr, S, nullptr, tid);
+    tile_commit<64 * NW, NKS2 * 32>(kr, Kb, tid);
+    tile_commit<64 * NW, NKS2 * 32>(vr, Vb, tid);
   }
   __syncthreads();
 
@@ -153,7 +154,7 @@ __global__ __launch_bounds__(64 * NW, NKT > 13 ? 2 : (NW + 1) / 2) void attn_fwd
     // softmax over the lane's 4*NKT keys.  exp(scale*s - max) is evaluated as exp2(fma(s, c, -max*c)) with
     // c = scale*log2(e) (one FMA + one v_exp per element); P stays un-normalised (<= 1) and the 16 output values are
     // scaled by 1/sum instead of the 4*NKT probabilities.  Only tiles that can hold masked keys pay for the select.
-    const float c = p.scale * 1.4426950408889634f;
+    const float c = p.scale * LOG2E;
     float mx = -INFINITY;
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt)
@@ -167,8 +168,7 @@ __global__ __launch_bounds__(64 * NW, NKT > 13 ? 2 : (NW + 1) / 2) void attn_fwd
         }
         mx = fmaxf(mx, sc[kt][r]);
       }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    mx = q4_max(mx);
     const float mref = (mx == -INFINITY) ? 0.f : mx;      // raw-score maximum (scale > 0)
     const float mc = mref * c;
     float sum = 0.f;
@@ -180,8 +180,7 @@ __global__ __launch_bounds__(64 * NW, NKT > 13 ? 2 : (NW + 1) / 2) void attn_fwd
         sc[kt][r] = e;
         sum += e;
       }
-    sum += __shfl_xor(sum, 16, 64);
-    sum += __shfl_xor(sum, 32, 64);
+    sum = q4_sum(sum);
     const float inv = sum > 0.f ? 1.0f / sum : 0.f;
 
     f32x4 oacc[4];
@@ -205,13 +204,7 @@ __global__ __launch_bounds__(64 * NW, NKT > 13 ? 2 : (NW + 1) / 2) void attn_fwd
     }
     if (query < S) {
       op_t* op = tok_ptr(p.o, p.o_cls, p.ldo, p.mp, sr, seq, query) + h * 64 + 4 * q4;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        opx4 ov;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) ov[r] = (op_t)(oacc[dt][r] * inv);
-        *reinterpret_cast<opx4*>(op + 16 * dt) = ov;
-      }
+      store_acc(op, oacc, inv);
       if (q4 == 0 && p.lse) p.lse[((long)seq * p.H + h) * S + query] = mref * p.scale + __logf(sum);
     }
   }
@@ -227,20 +220,10 @@ __global__ __launch_bounds__(64 * NW, NKT > 13 ? 2 : (NW + 1) / 2) void attn_bwd
   __shared__ __attribute__((aligned(16))) char smem[2 * BL];
   char* Kb = smem;
   char* Vb = smem + BL;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // workgroups are dealt round-robin to the 8 XCDs: keep the H heads of a sequence on ONE XCD, back to back, so the
-  // 128-byte head slices of a token row are fetched together (same DRAM pages, same L2)
-  const int xj = blockIdx.x >> 3;
-  const int seq = (xj / p.H) * 8 + (blockIdx.x & 7), h = xj % p.H;
-  if (seq >= p.nseq) return;
-  const int S = SC ? SC : p.mp.S;     // SC: the sequence length as a compile-time constant (0 = run time)
-  const int HD = p.H * PVRL_HEAD_DIM;
-  const SeqRows sr = seq_rows(p.mp, seq);
+  ATTN_WG_PROLOGUE(p, SC);
   constexpr int MAXT = (NKT + NW - 1) / NW;   // query tiles per wave
-  const int q4 = lane >> 4, i = lane & 15;
   const int nqt = (S + 15) >> 4;
-  const float c = p.scale * 1.4426950408889634f;
+  const float c = p.scale * LOG2E;
   // every global load of the workgroup goes out before the first wait: q / dO / O / lse of this wave's query tiles,
   // then the K and V head slices
   opx8 qf[MAXT][2], df[MAXT][2];
@@ -252,32 +235,28 @@ __global__ __launch_bounds__(64 * NW, NKT > 13 ? 2 : (NW + 1) / 2) void attn_bwd
       const int query = (wave + t * NW) * 16 + i;
       const int qj = query < S ? query : S - 1;
       const op_t* qp = p.qkv + row_of(sr, qj) * p.ld + h * 64 + q4 * 8;
-      qf[t][0] = *reinterpret_cast<const opx8*>(qp);
-      qf[t][1] = *reinterpret_cast<const opx8*>(qp + 32);
+      row_frags(qp, qf[t][0], qf[t][1]);
       const op_t* dop = tok_ptr(p.d_o, p.d_o_cls, p.ldo, p.mp, sr, seq, qj) + h * 64 + q4 * 8;
-      df[t][0] = *reinterpret_cast<const opx8*>(dop);
-      df[t][1] = *reinterpret_cast<const opx8*>(dop + 32);
+      row_frags(dop, df[t][0], df[t][1]);
       const op_t* ofp = tok_ptr(p.ofw, p.ofw_cls, p.ldo, p.mp, sr, seq, qj) + h * 64 + q4 * 8;
-      of[t][0] = *reinterpret_cast<const opx8*>(ofp);
-      of[t][1] = *reinterpret_cast<const opx8*>(ofp + 32);
-      lse2[t] = p.lse[((long)seq * p.H + h) * S + qj] * 1.4426950408889634f;
+      row_frags(ofp, of[t][0], of[t][1]);
+      lse2[t] = p.lse[((long)seq * p.H + h) * S + qj] * LOG2E;
     }
     TileRegs<64 * NW, NKS2 * 32> kr, vr;
-    tile_issue<64 * NW, NKS2 * 32>(kr, p.qkv, p.ld, HD + h * 64, sr, S, nullptr, NKS2 * 32, tid);
-    tile_issue<64 * NW, NKS2 * 32>(vr, p.qkv, p.ld, 2 * HD + h * 64, sr, S, nullptr, NKS2 * 32, tid);
+    tile_issue<64 * NW, NKS2 * 32>(kr, p.qkv, p.ld, HD + h * 64, sr, S, nullptr, tid);
+    tile_issue<64 * NW, NKS2 * 32>(vr, p.qkv, p.ld, 2 * HD + h * 64, sr, S, nullptr, tid);
 #pragma unroll
     for (int t = 0; t < MAXT; ++t) {
       float dsum = 0.f;
 #pragma unroll
       for (int e = 0; e < 8; ++e) dsum += (float)df[t][0][e] * (float)of[t][0][e] + (float)df[t][1][e] * (float)of[t][1][e];
-      dsum += __shfl_xor(dsum, 16, 64);
-      dsum += __shfl_xor(dsum, 32, 64);
+      dsum = q4_sum(dsum);
       dss[t] = dsum * p.scale;
       const int query = (wave + t * NW) * 16 + i;
       if (q4 == 0 && query < S) p.dvec[((long)seq * p.H + h) * S + query] = dsum;
     }
-    tile_commit<64 * NW, NKS2 * 32>(kr, Kb, NKS2 * 32, tid);
-    tile_commit<64 * NW, NKS2 * 32>(vr, Vb, NKS2 * 32, tid);
+    tile_commit<64 * NW, NKS2 * 32>(kr, Kb, tid);
+    tile_commit<64 * NW, NKS2 * 32>(vr, Vb, tid);
   }
   __syncthreads();
 
@@ -305,28 +284,19 @@ __global__ __launch_bounds__(64 * NW, NKT > 13 ? 2 : (NW + 1) / 2) void attn_bwd
           for (int r = 0; r < 4; ++r) sf[4 * half + r] = (op_t)0.f;
           continue;
         }
-        const int krow = kt * 16 + i;
-        const opx8 k0 = bl_row_frag(Kb, krow, q4);
-        const opx8 k1 = bl_row_frag(Kb, krow, 4 + q4);
-        const opx8 v0 = bl_row_frag(Vb, krow, q4);
-        const opx8 v1 = bl_row_frag(Vb, krow, 4 + q4);
-        f32x4 s = (f32x4){0.f, 0.f, 0.f, 0.f};
-        s = MFMA_16x16x32(k0, qf0, s, 0, 0, 0);
-        s = MFMA_16x16x32(k1, qf1, s, 0, 0, 0);
-        f32x4 dp = (f32x4){0.f, 0.f, 0.f, 0.f};
-        dp = MFMA_16x16x32(v0, df0, dp, 0, 0, 0);
-        dp = MFMA_16x16x32(v1, df1, dp, 0, 0, 0);
+        f32x4 s, dp;
+        s_dp_tile(Kb, Vb, kt * 16 + i, q4, qf0, qf1, df0, df1, s, dp);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int key = kt * 16 + 4 * q4 + r;
-          float pr = __builtin_amdgcn_exp2f(fmaf(s[r], c, -lse2_t));
+          float pr = p_from_lse(s[r], c, lse2_t);
           // (a padded query, query >= S, needs no mask: its lane's dS only feeds that lane's own dq, which is never stored)
           if (GEN || kt * 16 + 15 >= S) {
             bool msk = key >= S || (GEN && query >= S);
             if constexpr (GEN) msk = msk || ((pbits >> (kt * 4 + r)) & 1ull) || (p.causal && key > query);
             if (msk) pr = 0.f;
           }
-          sf[4 * half + r] = (op_t)(pr * fmaf(dp[r], p.scale, -dss_t));
+          sf[4 * half + r] = (op_t)ds_of(pr, dp[r], p.scale, dss_t);
         }
       }
 #pragma unroll
@@ -338,13 +308,7 @@ __global__ __launch_bounds__(64 * NW, NKT > 13 ? 2 : (NW + 1) / 2) void attn_bwd
     }
     if (query < S) {
       op_t* op = tok_ptr(p.dqkv, p.dqkv_cls, p.ldd, p.mp, sr, seq, query) + h * 64 + 4 * q4;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        opx4 ov;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) ov[r] = (op_t)dq[dt][r];
-        *reinterpret_cast<opx4*>(op + 16 * dt) = ov;
-      }
+      store_acc(op, dq);
     }
   }
 }
@@ -363,19 +327,9 @@ __global__ __launch_bounds__(64 * NW, NKT > 13 ? 2 : (NW + 1) / 2) void attn_bwd
   char* Db = smem + T;
   float* lse_s = reinterpret_cast<float*>(smem + 2 * T);
   float* dv_s = lse_s + ROWS;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // workgroups are dealt round-robin to the 8 XCDs: keep the H heads of a sequence on ONE XCD, back to back, so the
-  // 128-byte head slices of a token row are fetched together (same DRAM pages, same L2)
-  const int xj = blockIdx.x >> 3;
-  const int seq = (xj / p.H) * 8 + (blockIdx.x & 7), h = xj % p.H;
-  if (seq >= p.nseq) return;
-  const int S = SC ? SC : p.mp.S;     // SC: the sequence length as a compile-time constant (0 = run time)
-  const int HD = p.H * PVRL_HEAD_DIM;
-  const SeqRows sr = seq_rows(p.mp, seq);
+  ATTN_WG_PROLOGUE(p, SC);
   constexpr int MAXT = (NKT + NW - 1) / NW;   // key tiles per wave
-  const int q4 = lane >> 4, i = lane & 15;
-  const float c = p.scale * 1.4426950408889634f;
+  const float c = p.scale * LOG2E;
   const int nkt_rt = (S + 15) >> 4;
   // every global load of the workgroup goes out before the first wait: this wave's K / V fragments, then Q and dO
   opx8 kf[MAXT][2], vf[MAXT][2];
@@ -384,23 +338,21 @@ __global__ __launch_bounds__(64 * NW, NKT > 13 ? 2 : (NW + 1) / 2) void attn_bwd
     const int key = (wave + t * NW) * 16 + i;
     const int kj = key < S ? key : S - 1;
     const op_t* kp = p.qkv + row_of(sr, kj) * p.ld + HD + h * 64 + q4 * 8;
-    kf[t][0] = *reinterpret_cast<const opx8*>(kp);
-    kf[t][1] = *reinterpret_cast<const opx8*>(kp + 32);
-    vf[t][0] = *reinterpret_cast<const opx8*>(kp + HD);
-    vf[t][1] = *reinterpret_cast<const opx8*>(kp + HD + 32);
+    row_frags(kp, kf[t][0], kf[t][1]);
+    row_frags(kp + HD, vf[t][0], vf[t][1]);
   }
   {
     const op_t* src0 = p.mp.mode == 1 ? p.d_o_cls + (long)seq * p.ldo : nullptr;   // dO of token 0 lives in the side buffer
     TileRegs<64 * NW, ROWS> qr, dr;
-    tile_issue<64 * NW, ROWS>(qr, p.qkv, p.ld, h * 64, sr, S, nullptr, ROWS, tid);
-    tile_issue<64 * NW, ROWS>(dr, p.d_o, p.ldo, h * 64, sr, S, src0, ROWS, tid);
+    tile_issue<64 * NW, ROWS>(qr, p.qkv, p.ld, h * 64, sr, S, nullptr, tid);
+    tile_issue<64 * NW, ROWS>(dr, p.d_o, p.ldo, h * 64, sr, S, src0, tid);
     for (int idx = tid; idx < ROWS; idx += 64 * NW) {
       const long stat = ((long)seq * p.H + h) * S + idx;
-      lse_s[idx] = idx < S ? p.lse[stat] * 1.4426950408889634f : 0.f;
+      lse_s[idx] = idx < S ? p.lse[stat] * LOG2E : 0.f;
       dv_s[idx] = idx < S ? p.dvec[stat] * p.scale : 0.f;
     }
-    tile_commit<64 * NW, ROWS>(qr, Qb, ROWS, tid);
-    tile_commit<64 * NW, ROWS>(dr, Db, ROWS, tid);
+    tile_commit<64 * NW, ROWS>(qr, Qb, tid);
+    tile_commit<64 * NW, ROWS>(dr, Db, tid);
   }
   __syncthreads();
 
@@ -423,6 +375,7 @@ __global__ __launch_bounds__(64 * NW, NKT > 13 ? 2 : (NW + 1) / 2) void attn_bwd
       opx8 pf, sf;
 #pragma unroll
       for (int half = 0; half < 2; ++half) {
+        // (spelt out, not s_dp_tile: through the helper the NKT = 3 instantiations lose one s_movk_i32 and one s_waitcnt)
         const int qrow = (2 * u + half) * 16 + i;   // a-operand row: query
         const opx8 a0 = bl_row_frag(Qb, qrow, q4);
         const opx8 a1 = bl_row_frag(Qb, qrow, 4 + q4);
@@ -443,9 +396,9 @@ __global__ __launch_bounds__(64 * NW, NKT > 13 ? 2 : (NW + 1) / 2) void attn_bwd
           const int query = qb + r;
           bool msk = query >= S || kbad;
           if constexpr (GEN) msk = msk || (p.causal && key > query);
-          const float pr = msk ? 0.f : __builtin_amdgcn_exp2f(fmaf(s[r], c, -l4[r]));
+          const float pr = msk ? 0.f : p_from_lse(s[r], c, l4[r]);
           pf[half * 4 + r] = (op_t)pr;
-          sf[half * 4 + r] = (op_t)(pr * fmaf(dp[r], p.scale, -d4[r]));
+          sf[half * 4 + r] = (op_t)ds_of(pr, dp[r], p.scale, d4[r]);
         }
       }
 #pragma unroll
@@ -458,14 +411,7 @@ __global__ __launch_bounds__(64 * NW, NKT > 13 ? 2 : (NW + 1) / 2) void attn_bwd
     }
     if (key < S) {
       op_t* op = tok_ptr(p.dqkv, p.dqkv_cls, p.ldd, p.mp, sr, seq, key) + HD + h * 64 + 4 * q4;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        opx4 ok, ov;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { ok[r] = (op_t)dk[dt][r]; ov[r] = (op_t)dv[dt][r]; }
-        *reinterpret_cast<opx4*>(op + 16 * dt) = ok;
-        *reinterpret_cast<opx4*>(op + HD + 16 * dt) = ov;
-      }
+      store_acc2(op, dk, op + HD, dv);
     }
   }
 }
@@ -478,38 +424,47 @@ int check_common(const AttnArgs& p) {
   return PVRL_OK;
 }
 
+// run-time (S, masks) -> the instantiation of the three kernels that serves them: with_inst calls f(Inst<NKT, GEN, NW, SC>{})
+template <int NKT, bool GEN, int NW, int SC>
+struct Inst {};
+
 // The two sequence lengths of the TimeSformer path at its benchmark geometry -- 197 (196 patches + cls, spatial) and 32 (temporal,
 // long clips) -- are instantiated with S as a compile-time constant: `key >= S` is then false for every key tile but the last
 // (none at S = 32), so 12 of 13 tiles lose their per-score compare + select, and the 52 64-bit lane masks that spilled the
 // kernels' scalar registers into v_writelane / v_readlane pairs (SGPR spills 66 / 58 -> 0) disappear with them.
-template <int NKT, int NW>
-int launch_fwd(const AttnArgs& p, hipStream_t s) {
-  const dim3 grid((unsigned)(8 * ((p.nseq + 7) / 8) * p.H)), blk(64 * NW);
+template <int NKT, int NW, typename F>
+int with_form(const AttnArgs& p, F&& f) {
   constexpr int SFIX = NKT == 13 ? 197 : NKT == 2 ? 32 : 0;
-  if (p.causal || p.kpm) hipLaunchKernelGGL((attn_fwd_kernel<NKT, true, NW>), grid, blk, 0, s, p);
-  else if (SFIX && p.mp.S == SFIX) hipLaunchKernelGGL((attn_fwd_kernel<NKT, false, NW, SFIX>), grid, blk, 0, s, p);
-  else hipLaunchKernelGGL((attn_fwd_kernel<NKT, false, NW>), grid, blk, 0, s, p);
+  if (p.causal || p.kpm) return f(Inst<NKT, true, NW, 0>{});
+  if (SFIX && p.mp.S == SFIX) return f(Inst<NKT, false, NW, SFIX>{});
+  return f(Inst<NKT, false, NW, 0>{});
+}
+template <typename F>
+int with_inst(int64_t S, const AttnArgs& p, F&& f) {
+  if (S <= 16) return with_form<1, 4>(p, f);
+  if (S <= 32) return with_form<2, 4>(p, f);
+  if (S <= 48) return with_form<3, 4>(p, f);
+  if (S <= 80) return with_form<5, 4>(p, f);
+  if (S <= 208) return with_form<13, 8>(p, f);
+  // longer crops (256^2 -> 257 tokens, 320^2 -> 401): the same kernels with more key tiles, one 8-wave workgroup per CU
+  if (S <= 272) return with_form<17, 8>(p, f);
+  return with_form<26, 8>(p, f);
+}
+
+template <int NKT, bool GEN, int NW, int SC>
+int launch_fwd(Inst<NKT, GEN, NW, SC>, const AttnArgs& p, hipStream_t s) {
+  const dim3 grid((unsigned)(8 * ((p.nseq + 7) / 8) * p.H)), blk(64 * NW);
+  hipLaunchKernelGGL((attn_fwd_kernel<NKT, GEN, NW, SC>), grid, blk, 0, s, p);
   PVRL_LAUNCH_CHECK();
   return PVRL_OK;
 }
 
-template <int NKT, int NW>
-int launch_bwd(const AttnArgs& p, hipStream_t s) {
+template <int NKT, bool GEN, int NW, int SC>
+int launch_bwd(Inst<NKT, GEN, NW, SC>, const AttnArgs& p, hipStream_t s) {
   const dim3 grid((unsigned)(8 * ((p.nseq + 7) / 8) * p.H)), blk(64 * NW);
-  constexpr int SFIX = NKT == 13 ? 197 : NKT == 2 ? 32 : 0;
-  if (p.causal || p.kpm) {
-    hipLaunchKernelGGL((attn_bwd_q_kernel<NKT, true, NW>), grid, blk, 0, s, p);
-    PVRL_LAUNCH_CHECK();
-    hipLaunchKernelGGL((attn_bwd_kv_kernel<NKT, true, NW>), grid, blk, 0, s, p);
-  } else if (SFIX && p.mp.S == SFIX) {
-    hipLaunchKernelGGL((attn_bwd_q_kernel<NKT, false, NW, SFIX>), grid, blk, 0, s, p);
-    PVRL_LAUNCH_CHECK();
-    hipLaunchKernelGGL((attn_bwd_kv_kernel<NKT, false, NW, SFIX>), grid, blk, 0, s, p);
-  } else {
-    hipLaunchKernelGGL((attn_bwd_q_kernel<NKT, false, NW>), grid, blk, 0, s, p);
-    PVRL_LAUNCH_CHECK();
-    hipLaunchKernelGGL((attn_bwd_kv_kernel<NKT, false, NW>), grid, blk, 0, s, p);
-  }
+  hipLaunchKernelGGL((attn_bwd_q_kernel<NKT, GEN, NW, SC>), grid, blk, 0, s, p);
+  PVRL_LAUNCH_CHECK();
+  hipLaunchKernelGGL((attn_bwd_kv_kernel<NKT, GEN, NW, SC>), grid, blk, 0, s, p);
   PVRL_LAUNCH_CHECK();
   return PVRL_OK;
 }
@@ -519,36 +474,19 @@ int launch_bwd(const AttnArgs& p, hipStream_t s) {
 extern "C" int pvrl_attn_fwd(const void* qkv, int64_t ld, int64_t nseq, int64_t S, int64_t H, int mode, int64_t T,
                              int64_t cls_base, float scale, int causal, const void* key_padding_mask, void* o,
                              void* o_cls, int64_t ldo, float* lse, void* stream) {
-  AttnArgs p = {};
-  p.qkv = (const op_t*)qkv; p.ld = ld; p.H = (int)H; p.nseq = (int)nseq;
-  p.mp.mode = mode; p.mp.S = (int)S; p.mp.T = (int)T; p.mp.cls_base = cls_base;
-  p.scale = scale; p.causal = causal; p.kpm = (const unsigned char*)key_padding_mask;
-  p.o = (op_t*)o; p.o_cls = (op_t*)o_cls; p.ldo = ldo; p.lse = lse;
+  const AttnArgs p = attn_args(qkv, ld, nseq, S, H, mode, T, cls_base, scale, causal, key_padding_mask, o, o_cls, ldo, lse);
   if (nseq == 0) return PVRL_OK;
   if (int e = check_common(p)) return e;
   if (!o || (ldo % 4) || (mode == 1 && !o_cls)) return PVRL_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  if (S <= 16) return launch_fwd<1, 4>(p, s);
-  if (S <= 32) return launch_fwd<2, 4>(p, s);
-  if (S <= 48) return launch_fwd<3, 4>(p, s);
-  if (S <= 80) return launch_fwd<5, 4>(p, s);
-  if (S <= 208) return launch_fwd<13, 8>(p, s);
-  // longer crops (256^2 -> 257 tokens, 320^2 -> 401): the same kernels with more key tiles, one 8-wave workgroup per CU
-  if (S <= 272) return launch_fwd<17, 8>(p, s);
-  return launch_fwd<26, 8>(p, s);
+  return with_inst(S, p, [&](auto inst) { return launch_fwd(inst, p, (hipStream_t)stream); });
 }
 
 extern "C" int pvrl_attn_bwd(const void* qkv, int64_t ld, int64_t nseq, int64_t S, int64_t H, int mode, int64_t T,
                              int64_t cls_base, float scale, int causal, const void* key_padding_mask, const void* o,
                              const void* o_cls, const void* d_o, const void* d_o_cls, int64_t ldo, const float* lse,
                              float* dvec, void* dqkv, void* dqkv_cls, int64_t ldd, void* stream) {
-  AttnArgs p = {};
-  p.qkv = (const op_t*)qkv; p.ld = ld; p.H = (int)H; p.nseq = (int)nseq;
-  p.mp.mode = mode; p.mp.S = (int)S; p.mp.T = (int)T; p.mp.cls_base = cls_base;
-  p.scale = scale; p.causal = causal; p.kpm = (const unsigned char*)key_padding_mask;
-  p.ofw = (const op_t*)o; p.ofw_cls = (const op_t*)o_cls; p.d_o = (const op_t*)d_o; p.d_o_cls = (const op_t*)d_o_cls;
-  p.ldo = ldo; p.lse = const_cast<float*>(lse); p.dvec = dvec;
-  p.dqkv = (op_t*)dqkv; p.dqkv_cls = (op_t*)dqkv_cls; p.ldd = ldd;
+  const AttnArgs p = attn_args_bwd(qkv, ld, nseq, S, H, mode, T, cls_base, scale, causal, key_padding_mask, o, o_cls, d_o, d_o_cls,
+                                   ldo, lse, dvec, dqkv, dqkv_cls, ldd);
   if (nseq == 0) return PVRL_OK;
   if (int e = check_common(p)) return e;
   if (!o || !d_o || !lse || !dvec || !dqkv || (ldo % 8) || (ldd % 4)) return PVRL_EINVAL;
@@ -556,11 +494,5 @@ extern "C" int pvrl_attn_bwd(const void* qkv, int64_t ld, int64_t nseq, int64_t 
   hipStream_t s = (hipStream_t)stream;
   if (pvrl_attn_bwd_fused_ok(p)) return pvrl_attn_bwd_fused_launch(p, s);
   if (pvrl_attn_bwd_s32_ok(p)) return pvrl_attn_bwd_s32_launch(p, s);
-  if (S <= 16) return launch_bwd<1, 4>(p, s);
-  if (S <= 32) return launch_bwd<2, 4>(p, s);
-  if (S <= 48) return launch_bwd<3, 4>(p, s);
-  if (S <= 80) return launch_bwd<5, 4>(p, s);
-  if (S <= 208) return launch_bwd<13, 8>(p, s);
-  if (S <= 272) return launch_bwd<17, 8>(p, s);
-  return launch_bwd<26, 8>(p, s);
+  return with_inst(S, p, [&](auto inst) { return launch_bwd(inst, p, s); });
 }

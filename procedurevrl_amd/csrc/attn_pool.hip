@@ -25,7 +25,6 @@ constexpr int TILE_BYTES = KT * D * 2;  // 6 KiB
 constexpr int JMAX = 40;                // kh + kw + kt <= 36 (14 + 14 + 8); the d-rel MFMA covers 48 columns
 constexpr int MAXKEYS = 1664;           // 8*14*14 + 1 = 1569 keys, rounded
 constexpr int ET_BYTES = KT * 64 * 2;   // key-map tile [32 keys][64 j], blocked layout (bl_off): 4 KiB
-constexpr float LOG2E = 1.4426950408889634f;
 
 struct PA {
   const op_t* q; const op_t* k; const op_t* v;   // [BH][L+1][96]

@@ -42,7 +42,7 @@ __global__ __launch_bounds__(448, 2) void attn_fwd_stream_kernel(AttnArgs p, int
   const int nkt = (S + 31) >> 5;
   const int HD = p.H * 64;
   const int n = lane & 31, g = lane >> 5;
-  const float c = p.scale * 1.4426950408889634f;
+  const float c = p.scale * LOG2E;
   const unsigned ldsbase = __builtin_amdgcn_readfirstlane(lds_addr(smem));
   const bool qwave = wave < nkt;                 // this wave owns queries of the sequence
 
