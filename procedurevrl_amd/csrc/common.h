@@ -172,6 +172,14 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// workgroups of 256 threads for `total` work items of a grid-stride kernel (mvit.hip, mvit_rel.hip)
+static inline unsigned grid_blocks(long total) {
+  long b = (total + 255) / 256;
+  if (b < 1) b = 1;
+  if (b > 65535L * 16) b = 65535L * 16;
+  return (unsigned)b;
+}
+
 // CUs per XCD that the PERSISTENT / one-round kernels of this library size their grids for (gemm_nt8, gemm_tn8 and its grouped
 // launch, attn_bwd_fused: one 512-thread workgroup owns a whole CU -- 256 VGPRs per lane, 128 KB of LDS).  Default: all of them
 // (MI355X: 256 CUs / 8 XCDs = 32).  PVRL_COMPUTE_CUS=<n> (read once per process: the one piece of process-wide

@@ -14,13 +14,6 @@ namespace {
 
 constexpr int HD = PVRL_MVIT_HEAD_DIM;   // head_dim of every MViTv2 block (96/1, 192/2, 384/4, 768/8)
 
-inline unsigned grid_for(long total, int per_block = 256) {
-  long b = (total + per_block - 1) / per_block;
-  if (b < 1) b = 1;
-  if (b > 65535L * 16) b = 65535L * 16;
-  return (unsigned)b;
-}
-
 // ------------------------------------------------------------------------------------------------- im2col 3-D
 struct Conv3dGeom {
   int B, Cin, T, H, W, kt, kh, kw, st, sh, sw, pt, ph, pw, To, Ho, Wo, K;   // K = Cin*kt*kh*kw
@@ -96,7 +89,6 @@ __global__ __launch_bounds__(256) void im2col3d_rows_kernel(const float* __restr
   __shared__ unsigned lca[IMR_LINES];             // line -> c << 16 | a << 8 | y
   const int tid = threadIdx.x;
   const int nline = g.Cin * g.kt * g.kh;
-  const int khw = g.kh * g.kw;
   for (int k = tid; k < (int)ldo; k += 256) {
     unsigned e = 0xffffffffu;
     if (k < g.K) {
@@ -111,7 +103,6 @@ __global__ __launch_bounds__(256) void im2col3d_rows_kernel(const float* __restr
   }
   for (int i = tid; i < IMR_LINES * IMR_PITCH / 2; i += 256) reinterpret_cast<unsigned*>(&lines[0][0])[i] = 0u;   // borders stay zero
   __syncthreads();
-  (void)khw;
   const long plane = (long)g.H * g.W;
   const int w4 = g.W >> 2, chunks = (int)(ldo >> 3);
   const int lrow = tid >> 6, j = tid & 63;
@@ -390,6 +381,87 @@ __device__ __forceinline__ float sum16(float v) {   // over the 16 lanes that sh
   return v;
 }
 
+// ---- the pieces every kernel of the family shares ----
+// depthwise weights w[c][27] -> LDS ws[tap][c], visible to the whole (256-thread) workgroup on return
+__device__ __forceinline__ void pool_stage_weights(float* ws, const float* __restrict__ w) {
+  for (int i = threadIdx.x; i < 27 * HD; i += 256) ws[i] = w[(i % HD) * 27 + i / HD];
+  __syncthreads();
+}
+// id = (b * H + h) * n + pos  ->  pos, bh = b * H + h, h, b.  I = unsigned wherever the launcher bounds the count: 64-bit
+// divisions cost ~100 VALU instructions each
+template <typename I>
+__device__ __forceinline__ void pool_decode(I id, int n, int H, int& pos, I& bh, int& h, int& b) {
+  pos = (int)(id % (I)n);
+  bh = id / (I)n;
+  h = (int)(bh % (I)H);
+  b = (int)(bh / (I)H);
+}
+// LayerNorm(96) statistics of one token: 16 lanes x 6 channels
+__device__ __forceinline__ void pool_ln_stats(const float (&v)[6], float eps, float& mu, float& rs) {
+  float s = 0.f;
+#pragma unroll
+  for (int e = 0; e < 6; ++e) s += v[e];
+  mu = sum16(s) * (1.f / HD);
+  float q = 0.f;
+#pragma unroll
+  for (int e = 0; e < 6; ++e) q += (v[e] - mu) * (v[e] - mu);
+  rs = rsqrtf(sum16(q) * (1.f / HD) + eps);
+}
+// conv output -> cdst (kept for the backward), its LayerNorm -> ydst
+__device__ __forceinline__ void pool_ln_store(const float (&acc)[6], const float (&gm)[6], const float (&bt)[6], float eps,
+                                              op_t* cdst, op_t* ydst) {
+  st6(cdst, acc);
+  float mu, rs;
+  pool_ln_stats(acc, eps, mu, rs);
+  float o[6];
+#pragma unroll
+  for (int e = 0; e < 6; ++e) o[e] = (acc[e] - mu) * rs * gm[e] + bt[e];
+  st6(ydst, o);
+}
+// The next three are macros on purpose: as inline functions that take the arrays by reference the same text compiles to other
+// code in the sliding kernels (the frame loop is no longer peeled, other register counts).
+// row offset (yi * Ww + xi) of the 9 in-plane inputs of output position (yo, xo) of PoolGeom g, -1 = outside
+#define POOL_IN_PLANE(noff, g, yo, xo)                                                                                 \
+  _Pragma("unroll") for (int yy = 0; yy < 3; ++yy)                                                                     \
+    _Pragma("unroll") for (int xx = 0; xx < 3; ++xx) {                                                                 \
+      const int yi = yo * g.sh - 1 + yy, xi = xo * g.sw - 1 + xx;                                                      \
+      noff[yy * 3 + xx] = (yi >= 0 && yi < g.Hh && xi >= 0 && xi < g.Ww) ? yi * g.Ww + xi : -1;                        \
+    }
+// One frame of a t-sliding kernel: the rows frame + noff[n] * pitch (9 in-plane neighbours, noff < 0 = none) are loaded once
+// and meet the taps a = 0 / 1 / 2 of ws (tap (a, yy, xx) at ws[a*9 + n][c]), accumulated into a0 / a1 / a2 -- the running sums
+// of three consecutive frames, in the order the caller's direction needs.
+// DENSE: all nine neighbour loads issued together from clamped addresses, an absent neighbour zeroed by a select, and wbase made
+// opaque per frame, so that the 162 weights stay in LDS instead of 162 hoisted VGPRs; otherwise the loads are guarded (one wait
+// each, absent neighbours skipped).  Which form wins where: at the two kernels.
+#define POOL_FRAME_STEP(DENSE, frame, pitch, noff, ws, c0, a0, a1, a2)                                                 \
+  do {                                                                                                                 \
+    const op_t* pb = (frame);                                                                                          \
+    Raw6 raw[9];                                                                                                       \
+    int wbase = c0;                                                                                                    \
+    if constexpr (DENSE) {                                                                                             \
+      _Pragma("unroll") for (int n = 0; n < 9; ++n) raw[n] = ld6_raw(pb + (long)max(noff[n], 0) * (pitch));           \
+      asm volatile("" : "+v"(wbase));                                                                                  \
+    }                                                                                                                  \
+    _Pragma("unroll") for (int n = 0; n < 9; ++n) {                                                                    \
+      float v[6];                                                                                                      \
+      if constexpr (DENSE) {                                                                                           \
+        unpack6(raw[n], noff[n] >= 0, v);                                                                              \
+      } else {                                                                                                         \
+        if (noff[n] < 0) continue;                                                                                     \
+        ld6(pb + (long)noff[n] * (pitch), v);                                                                          \
+      }                                                                                                                \
+      const float* w0 = ws + n * HD + wbase;                                                                           \
+      _Pragma("unroll") for (int e = 0; e < 6; ++e) {                                                                  \
+        a0[e] = fmaf(v[e], w0[e], a0[e]);                                                                              \
+        a1[e] = fmaf(v[e], w0[9 * HD + e], a1[e]);                                                                     \
+        a2[e] = fmaf(v[e], w0[18 * HD + e], a2[e]);                                                                    \
+      }                                                                                                                \
+    }                                                                                                                  \
+  } while (0)
+// ... and the step to the next frame, once the caller has stored the finished sum aP
+#define POOL_FRAME_SHIFT(aP, aC, aN) \
+  _Pragma("unroll") for (int e = 0; e < 6; ++e) { aP[e] = aC[e]; aC[e] = aN[e]; aN[e] = 0.f; }
+
 // y[bh][lo][96] = LayerNorm_96(conv3d_depthwise(x)[lo]) for lo < Lo, = LayerNorm_96(x_cls) for lo = Lo; conv output kept
 // (bf16) for the backward.  16 lanes per output token, 6 channels per lane.
 __global__ __launch_bounds__(256) void pool_fwd_kernel(const op_t* __restrict__ qkv, PoolGeom g,
@@ -397,8 +469,7 @@ __global__ __launch_bounds__(256) void pool_fwd_kernel(const op_t* __restrict__ 
                                                        const float* __restrict__ beta, float eps, op_t* __restrict__ y,
                                                        op_t* __restrict__ cbuf) {
   __shared__ float ws[27 * HD];
-  for (int i = threadIdx.x; i < 27 * HD; i += 256) ws[i] = w[(i % HD) * 27 + i / HD];   // [tap][c]
-  __syncthreads();
+  pool_stage_weights(ws, w);
   const int sub = threadIdx.x & 15, c0 = sub * 6;
   const int Lo = g.To * g.Ho * g.Wo, L = g.T * g.Hh * g.Ww;
   const unsigned ntok = (unsigned)((long)g.B * g.H * (Lo + 1));     // < 2^27 (checked by the launcher): 32-bit index math
@@ -410,9 +481,9 @@ __global__ __launch_bounds__(256) void pool_fwd_kernel(const op_t* __restrict__ 
   // block 0's q pooling, L2-miss-bound).  xcd_remap gives each XCD one contiguous run of tokens: its own three frames.
   const unsigned wg = (unsigned)xcd_remap((int)blockIdx.x, (int)gridDim.x);
   for (unsigned tok = (wg * 256u + threadIdx.x) >> 4; tok < ntok; tok += (gridDim.x * 256u) >> 4) {
-    const int lo = (int)(tok % (unsigned)(Lo + 1));
-    const unsigned bh = tok / (unsigned)(Lo + 1);
-    const int h = (int)(bh % (unsigned)g.H), b = (int)(bh / (unsigned)g.H);
+    int lo, h, b;
+    unsigned bh;
+    pool_decode(tok, Lo + 1, g.H, lo, bh, h, b);
     const int col = g.col0 + h * HD + c0;
     float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (lo == Lo) {
@@ -440,19 +511,7 @@ __global__ __launch_bounds__(256) void pool_fwd_kernel(const op_t* __restrict__ 
         }
       }
     }
-    st6(cbuf + (long)tok * HD + c0, acc);
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < 6; ++e) s += acc[e];
-    const float mu = sum16(s) * (1.f / HD);
-    float q = 0.f;
-#pragma unroll
-    for (int e = 0; e < 6; ++e) q += (acc[e] - mu) * (acc[e] - mu);
-    const float rs = rsqrtf(sum16(q) * (1.f / HD) + eps);
-    float o[6];
-#pragma unroll
-    for (int e = 0; e < 6; ++e) o[e] = (acc[e] - mu) * rs * gm[e] + bt[e];
-    st6(y + (long)tok * HD + c0, o);
+    pool_ln_store(acc, gm, bt, eps, cbuf + (long)tok * HD + c0, y + (long)tok * HD + c0);
   }
 }
 
@@ -461,31 +520,15 @@ __global__ __launch_bounds__(256) void pool_fwd_kernel(const op_t* __restrict__ 
 // for block 0's q pooling against ~100 us of memory time).  Here 16 lanes own one output COLUMN (b, h, yo, xo) and walk the
 // T input frames once: the 9 in-plane neighbours of a frame are loaded ONCE and feed three running sums (the outputs of the
 // frame before, this frame and the next: taps a = 2, 1, 0); a third of the loads, unpacks and address computations.
-__device__ __forceinline__ void pool_ln_store(const float (&acc)[6], const float (&gm)[6], const float (&bt)[6], float eps,
-                                              op_t* cdst, op_t* ydst) {
-  st6(cdst, acc);
-  float s = 0.f;
-#pragma unroll
-  for (int e = 0; e < 6; ++e) s += acc[e];
-  const float mu = sum16(s) * (1.f / HD);
-  float q = 0.f;
-#pragma unroll
-  for (int e = 0; e < 6; ++e) q += (acc[e] - mu) * (acc[e] - mu);
-  const float rs = rsqrtf(sum16(q) * (1.f / HD) + eps);
-  float o[6];
-#pragma unroll
-  for (int e = 0; e < 6; ++e) o[e] = (acc[e] - mu) * rs * gm[e] + bt[e];
-  st6(ydst, o);
-}
-
+// DENSE (pool_frame_step) is the form for the strided (k / v) pools, whose few columns cannot hide nine serial round trips
+// (36 -> 23 us); the guarded loads wait once each, but 118 VGPRs = 4 waves / SIMD: ahead on the dense stride-1 planes.
 template <bool DENSE>
 __global__ __launch_bounds__(256) void pool_fwd_t_kernel(const op_t* __restrict__ qkv, PoolGeom g,
                                                          const float* __restrict__ w, const float* __restrict__ gamma,
                                                          const float* __restrict__ beta, float eps, op_t* __restrict__ y,
                                                          op_t* __restrict__ cbuf) {
   __shared__ float ws[27 * HD];
-  for (int i = threadIdx.x; i < 27 * HD; i += 256) ws[i] = w[(i % HD) * 27 + i / HD];   // [tap][c]
-  __syncthreads();
+  pool_stage_weights(ws, w);
   const int sub = threadIdx.x & 15, c0 = sub * 6;
   const int HoWo = g.Ho * g.Wo, Lo = g.T * HoWo, L = g.T * g.Hh * g.Ww, plane = g.Hh * g.Ww;
   const unsigned ncol = (unsigned)((long)g.B * g.H * (HoWo + 1));      // + one "column" per (b, h) for the cls token
@@ -494,9 +537,9 @@ __global__ __launch_bounds__(256) void pool_fwd_t_kernel(const op_t* __restrict_
   for (int e = 0; e < 6; ++e) { gm[e] = gamma[c0 + e]; bt[e] = beta[c0 + e]; }
   const unsigned wg = (unsigned)xcd_remap((int)blockIdx.x, (int)gridDim.x);
   for (unsigned colid = (wg * 256u + threadIdx.x) >> 4; colid < ncol; colid += (gridDim.x * 256u) >> 4) {
-    const int pos = (int)(colid % (unsigned)(HoWo + 1));
-    const unsigned bh = colid / (unsigned)(HoWo + 1);
-    const int h = (int)(bh % (unsigned)g.H), b = (int)(bh / (unsigned)g.H);
+    int pos, h, b;
+    unsigned bh;
+    pool_decode(colid, HoWo + 1, g.H, pos, bh, h, b);
     const int col = g.col0 + h * HD + c0;
     op_t* cdst = cbuf + (long)bh * (Lo + 1) * HD + c0;
     op_t* ydst = y + (long)bh * (Lo + 1) * HD + c0;
@@ -507,53 +550,20 @@ __global__ __launch_bounds__(256) void pool_fwd_t_kernel(const op_t* __restrict_
       continue;
     }
     const int xo = pos % g.Wo, yo = pos / g.Wo;
-    int noff[9];                                                      // row offset of the 9 in-plane neighbours, -1 = outside
-#pragma unroll
-    for (int yy = 0; yy < 3; ++yy)
-#pragma unroll
-      for (int xx = 0; xx < 3; ++xx) {
-        const int yi = yo * g.sh - 1 + yy, xi = xo * g.sw - 1 + xx;
-        noff[yy * 3 + xx] = (yi >= 0 && yi < g.Hh && xi >= 0 && xi < g.Ww) ? yi * g.Ww + xi : -1;
-      }
+    int noff[9];
+    POOL_IN_PLANE(noff, g, yo, xo)
     const op_t* base = qkv + (long)b * L * g.ld + col;
     float aP[6], aC[6], aN[6];                                        // running sums of outputs t-1, t, t+1
 #pragma unroll
     for (int e = 0; e < 6; ++e) { aP[e] = 0.f; aC[e] = 0.f; aN[e] = 0.f; }
     for (int ti = 0; ti < g.T; ++ti) {
-      const op_t* pb = base + (long)ti * plane * g.ld;
-      // DENSE: all nine neighbour loads issued together from clamped addresses, an outside neighbour zeroed by a select --
-      // the form for the strided (k / v) pools, whose few columns cannot hide nine serial round trips (36 -> 23 us);
-      // otherwise the loads are guarded (one wait each, but 118 VGPRs = 4 waves / SIMD: ahead on the dense stride-1 planes)
-      Raw6 raw[9];
-      int wbase = c0;
-      if constexpr (DENSE) {
-#pragma unroll
-        for (int n = 0; n < 9; ++n) raw[n] = ld6_raw(pb + (long)max(noff[n], 0) * g.ld);
-        asm volatile("" : "+v"(wbase));           // opaque per frame: the 162 weights stay in LDS instead of 162 hoisted VGPRs
-      }
-#pragma unroll
-      for (int n = 0; n < 9; ++n) {
-        float v[6];
-        if constexpr (DENSE) {
-          unpack6(raw[n], noff[n] >= 0, v);
-        } else {
-          if (noff[n] < 0) continue;
-          ld6(pb + (long)noff[n] * g.ld, v);
-        }
-        const float* w0 = ws + n * HD + wbase;                         // tap (a, yy, xx) at [(a*9 + n)][c]
-#pragma unroll
-        for (int e = 0; e < 6; ++e) {
-          aN[e] = fmaf(v[e], w0[e], aN[e]);                            // a = 0: this frame is the one BEFORE output ti + 1
-          aC[e] = fmaf(v[e], w0[9 * HD + e], aC[e]);                   // a = 1
-          aP[e] = fmaf(v[e], w0[18 * HD + e], aP[e]);                  // a = 2: this frame is the one AFTER output ti - 1
-        }
-      }
+      // tap a = 0: input frame ti is the one BEFORE output ti + 1; a = 2: the one AFTER output ti - 1
+      POOL_FRAME_STEP(DENSE, base + (long)ti * plane * g.ld, g.ld, noff, ws, c0, aN, aC, aP);
       if (ti >= 1) {
         const long o = ((long)(ti - 1) * HoWo + pos) * HD;
         pool_ln_store(aP, gm, bt, eps, cdst + o, ydst + o);
       }
-#pragma unroll
-      for (int e = 0; e < 6; ++e) { aP[e] = aC[e]; aC[e] = aN[e]; aN[e] = 0.f; }
+      POOL_FRAME_SHIFT(aP, aC, aN)
     }
     const long o = ((long)(g.T - 1) * HoWo + pos) * HD;
     pool_ln_store(aP, gm, bt, eps, cdst + o, ydst + o);
@@ -577,14 +587,8 @@ __global__ __launch_bounds__(256) void pool_ln_bwd_kernel(const op_t* __restrict
     float c[6], d[6];
     ld6(cbuf + tok * HD + c0, c);
     ld6(dy + tok * HD + c0, d);
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < 6; ++e) s += c[e];
-    const float mu = sum16(s) * (1.f / HD);
-    float q = 0.f;
-#pragma unroll
-    for (int e = 0; e < 6; ++e) q += (c[e] - mu) * (c[e] - mu);
-    const float rs = rsqrtf(sum16(q) * (1.f / HD) + eps);
+    float mu, rs;
+    pool_ln_stats(c, eps, mu, rs);
     float xh[6], gg[6], s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int e = 0; e < 6; ++e) {
@@ -601,10 +605,10 @@ __global__ __launch_bounds__(256) void pool_ln_bwd_kernel(const op_t* __restrict
 #pragma unroll
     for (int e = 0; e < 6; ++e) o[e] = rs * (gg[e] - s1 - xh[e] * s2);
     st6(dc + tok * HD + c0, o);
-    const int lo = (int)(tok % (Lo + 1));
+    int lo, h, b;
+    long bh;
+    pool_decode(tok, Lo + 1, g.H, lo, bh, h, b);
     if (lo == Lo) {
-      const long bh = tok / (Lo + 1);
-      const int h = (int)(bh % g.H), b = (int)(bh / g.H);
       st6(dqkv + (g.cls_row0 + b) * g.ld + g.col0 + h * HD + c0, o);
     }
   }
@@ -626,16 +630,15 @@ __global__ __launch_bounds__(256) void pool_ln_bwd_kernel(const op_t* __restrict
 __global__ __launch_bounds__(256) void pool_dgrad_kernel(const op_t* __restrict__ dc, PoolGeom g,
                                                          const float* __restrict__ w, op_t* __restrict__ dqkv) {
   __shared__ float ws[27 * HD];
-  for (int i = threadIdx.x; i < 27 * HD; i += 256) ws[i] = w[(i % HD) * 27 + i / HD];
-  __syncthreads();
+  pool_stage_weights(ws, w);
   const int sub = threadIdx.x & 15, c0 = sub * 6;
   const int Lo = g.To * g.Ho * g.Wo, L = g.T * g.Hh * g.Ww;
   const int st = g.st, sh = g.sh, sw = g.sw;
   const unsigned ntok = (unsigned)((long)g.B * g.H * L);          // < 2^31 (checked by the launcher)
   const unsigned wg = (unsigned)xcd_remap((int)blockIdx.x, (int)gridDim.x);     // contiguous tokens per XCD (see pool_fwd_kernel)
   for (unsigned tok = (wg * 256u + threadIdx.x) >> 4; tok < ntok; tok += (gridDim.x * 256u) >> 4) {
-    const unsigned l = tok % (unsigned)L, bh = tok / (unsigned)L;
-    const unsigned h = bh % (unsigned)g.H, b = bh / (unsigned)g.H;
+    const unsigned l = tok % (unsigned)L, bh = tok / (unsigned)L;          // (not pool_decode: l, h, b are unsigned in the address
+    const unsigned h = bh % (unsigned)g.H, b = bh / (unsigned)g.H;         //  arithmetic below, as ints it compiles to other code)
     const int xi = (int)(l % (unsigned)g.Ww), yi = (int)((l / (unsigned)g.Ww) % (unsigned)g.Hh), ti = (int)(l / (unsigned)(g.Ww * g.Hh));
     float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -676,16 +679,15 @@ template <bool DENSE, int S>
 __global__ __launch_bounds__(256) void pool_dgrad_t_kernel(const op_t* __restrict__ dc, PoolGeom g,
                                                            const float* __restrict__ w, op_t* __restrict__ dqkv) {
   __shared__ float ws[27 * HD];
-  for (int i = threadIdx.x; i < 27 * HD; i += 256) ws[i] = w[(i % HD) * 27 + i / HD];
-  __syncthreads();
+  pool_stage_weights(ws, w);
   const int sub = threadIdx.x & 15, c0 = sub * 6;
   const int HoWo = g.Ho * g.Wo, Lo = g.T * HoWo, plane = g.Hh * g.Ww, L = g.T * plane;
   const unsigned ncol = (unsigned)((long)g.B * g.H * plane);
   const unsigned wg = (unsigned)xcd_remap((int)blockIdx.x, (int)gridDim.x);
   for (unsigned colid = (wg * 256u + threadIdx.x) >> 4; colid < ncol; colid += (gridDim.x * 256u) >> 4) {
-    const int pos = (int)(colid % (unsigned)plane);
-    const unsigned bh = colid / (unsigned)plane;
-    const int h = (int)(bh % (unsigned)g.H), b = (int)(bh / (unsigned)g.H);
+    int pos, h, b;
+    unsigned bh;
+    pool_decode(colid, plane, g.H, pos, bh, h, b);
     const int xi = pos % g.Ww, yi = pos / g.Ww;
     int noff[9];                                   // output position (yo * Wo + xo) reached through tap (yy, xx), -1 = none
 #pragma unroll
@@ -703,36 +705,12 @@ __global__ __launch_bounds__(256) void pool_dgrad_t_kernel(const op_t* __restric
 #pragma unroll
     for (int e = 0; e < 6; ++e) { aP[e] = 0.f; aC[e] = 0.f; aN[e] = 0.f; }
     for (int to = 0; to < g.T; ++to) {
-      const op_t* pb = base + (long)to * HoWo * HD;
       // DENSE (spatial stride 1: all nine taps exist away from the border): see pool_fwd_t_kernel; with stride 2 / 4 / 8 an input meets
-      // at most four / one or two outputs and skipping the others (guarded loads) does less work (measured per stride)
-      Raw6 raw[9];
-      int wbase = c0;
-      if constexpr (DENSE) {
-#pragma unroll
-        for (int n = 0; n < 9; ++n) raw[n] = ld6_raw(pb + (long)max(noff[n], 0) * HD);
-        asm volatile("" : "+v"(wbase));
-      }
-#pragma unroll
-      for (int n = 0; n < 9; ++n) {
-        float v[6];
-        if constexpr (DENSE) {
-          unpack6(raw[n], noff[n] >= 0, v);
-        } else {
-          if (noff[n] < 0) continue;
-          ld6(pb + (long)noff[n] * HD, v);
-        }
-        const float* w0 = ws + n * HD + wbase;
-#pragma unroll
-        for (int e = 0; e < 6; ++e) {
-          aP[e] = fmaf(v[e], w0[e], aP[e]);                            // a = 0: output frame `to` reads input frame to - 1
-          aC[e] = fmaf(v[e], w0[9 * HD + e], aC[e]);                   // a = 1
-          aN[e] = fmaf(v[e], w0[18 * HD + e], aN[e]);                  // a = 2: ... and input frame to + 1
-        }
-      }
+      // at most four / one or two outputs and skipping the others (guarded loads) does less work (measured per stride).
+      // tap a = 0: output frame `to` reads input frame to - 1; a = 2: ... and input frame to + 1
+      POOL_FRAME_STEP(DENSE, base + (long)to * HoWo * HD, HD, noff, ws, c0, aP, aC, aN);
       if (to >= 1) st6(dst + (long)(to - 1) * plane * g.ld, aP);
-#pragma unroll
-      for (int e = 0; e < 6; ++e) { aP[e] = aC[e]; aC[e] = aN[e]; aN[e] = 0.f; }
+      POOL_FRAME_SHIFT(aP, aC, aN)
     }
     st6(dst + (long)(g.T - 1) * plane * g.ld, aP);
   }
@@ -742,13 +720,37 @@ __global__ __launch_bounds__(256) void pool_dgrad_t_kernel(const op_t* __restric
 // block = 8 token lanes x 24 channel quads (8-byte loads); each thread keeps 27 x 4 sums in registers (no atomics).  The 27 neighbour
 // loads of a token are unconditional (clamped address, 0/1 mask) so they are all in flight together.
 constexpr int PW_LANES = 8, PW_CQ = HD / 4;
+// r (f32x4) = the four packed operands of w (u32x2), zeros if !ok.  A macro: as an inline function it changes the fp16 flavour's
+// pool_wgrad_t_kernel (other register count), and so does evaluating `ok` once per word instead of once
+#define UNPACK4(r, w, ok)                                           \
+  do {                                                              \
+    const bool ok_ = (ok);                                          \
+    float a_, b_;                                                   \
+    op_unpack2(ok_ ? (w)[0] : 0u, a_, b_); r[0] = a_; r[1] = b_;    \
+    op_unpack2(ok_ ? (w)[1] : 0u, a_, b_); r[2] = a_; r[3] = b_;    \
+  } while (0)
 __device__ __forceinline__ f32x4 ld4bf(const op_t* p) {
   const u32x2 w = *reinterpret_cast<const u32x2*>(p);
   f32x4 r;
-  float a, b;
-  op_unpack2(w[0], a, b); r[0] = a; r[1] = b;
-  op_unpack2(w[1], a, b); r[2] = a; r[3] = b;
+  UNPACK4(r, w, true);
   return r;
+}
+// The 8 token lanes of a workgroup add their 27 x 4 sums into red (zeroed by the kernel before its token loop) one after
+// the other -- a fixed order -- and the workgroup writes its partial row, summed over workgroups by pool_wgrad_reduce_kernel.
+__device__ __forceinline__ void wgrad_flush(float (&red)[27][HD], const f32x4 (&acc)[27], int tl, int c0,
+                                            float* __restrict__ part) {
+  __syncthreads();
+  for (int k = 0; k < PW_LANES; ++k) {
+    if (tl == k) {
+#pragma unroll
+      for (int t = 0; t < 27; ++t)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) red[t][c0 + e] += acc[t][e];
+    }
+    __syncthreads();
+  }
+  float* mine = part + (long)blockIdx.x * (27 * HD);
+  for (int i = threadIdx.x; i < 27 * HD; i += PW_CQ * PW_LANES) mine[i] = red[i / HD][i % HD];
 }
 __global__ __launch_bounds__(PW_CQ * PW_LANES) void pool_wgrad_kernel(const op_t* __restrict__ dc,
                                                                       const op_t* __restrict__ qkv, PoolGeom g,
@@ -767,9 +769,9 @@ __global__ __launch_bounds__(PW_CQ * PW_LANES) void pool_wgrad_kernel(const op_t
   const long chunk = (ntok + gridDim.x - 1) / gridDim.x;
   const long tend = min(ntok, (wgl + 1) * chunk);
   for (long tok = wgl * chunk + tl; tok < tend; tok += PW_LANES) {
-    const int lo = (int)(tok % Lo);
-    const long bh = tok / Lo;
-    const int h = (int)(bh % g.H), b = (int)(bh / g.H);
+    int lo, h, b;
+    long bh;
+    pool_decode(tok, Lo, g.H, lo, bh, h, b);
     const int xo = lo % g.Wo, yo = (lo / g.Wo) % g.Ho, to = lo / (g.Wo * g.Ho);
     const f32x4 d = ld4bf(dc + (bh * (Lo + 1) + lo) * HD + c0);
     const op_t* xb = qkv + (long)b * L * g.ld + g.col0 + h * HD + c0;
@@ -794,18 +796,7 @@ __global__ __launch_bounds__(PW_CQ * PW_LANES) void pool_wgrad_kernel(const op_t
 #pragma unroll
     for (int t = 0; t < 27; ++t) acc[t] += d * xv[t];
   }
-  __syncthreads();
-  for (int k = 0; k < PW_LANES; ++k) {      // the 8 token lanes add their sums one after the other: a fixed order
-    if (tl == k) {
-#pragma unroll
-      for (int t = 0; t < 27; ++t)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) red[t][c0 + e] += acc[t][e];
-    }
-    __syncthreads();
-  }
-  float* mine = part + (long)blockIdx.x * (27 * HD);
-  for (int i = threadIdx.x; i < 27 * HD; i += PW_CQ * PW_LANES) mine[i] = red[i / HD][i % HD];
+  wgrad_flush(red, acc, tl, c0, part);
 }
 
 // The same for temporal stride 1, sliding along t: a token lane walks the T frames of one output COLUMN (b, h, yo, xo); the 9
@@ -826,18 +817,12 @@ __global__ __launch_bounds__(PW_CQ * PW_LANES) void pool_wgrad_t_kernel(const op
   const unsigned chunk = (ncol + gridDim.x - 1) / gridDim.x;
   const unsigned cend = min(ncol, (wgl + 1) * chunk);
   for (unsigned colid = wgl * chunk + tl; colid < cend; colid += PW_LANES) {
-    const int pos = (int)(colid % (unsigned)HoWo);
-    const unsigned bh = colid / (unsigned)HoWo;
-    const int h = (int)(bh % (unsigned)g.H), b = (int)(bh / (unsigned)g.H);
+    int pos, h, b;
+    unsigned bh;
+    pool_decode(colid, HoWo, g.H, pos, bh, h, b);
     const int xo = pos % g.Wo, yo = pos / g.Wo;
     int noff[9];
-#pragma unroll
-    for (int yy = 0; yy < 3; ++yy)
-#pragma unroll
-      for (int xx = 0; xx < 3; ++xx) {
-        const int yi = yo * g.sh - 1 + yy, xi = xo * g.sw - 1 + xx;
-        noff[yy * 3 + xx] = (yi >= 0 && yi < g.Hh && xi >= 0 && xi < g.Ww) ? yi * g.Ww + xi : -1;
-      }
+    POOL_IN_PLANE(noff, g, yo, xo)
     const op_t* xb = qkv + (long)b * L * g.ld + g.col0 + h * HD + c0;
     const op_t* db = dc + ((long)bh * (Lo + 1) + pos) * HD + c0;
     const f32x4 zero = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -860,9 +845,8 @@ __global__ __launch_bounds__(PW_CQ * PW_LANES) void pool_wgrad_t_kernel(const op
       const f32x4 d2 = ti + 2 < g.T ? l2 : zero, d3 = ti + 3 < g.T ? l3 : zero;
 #pragma unroll
       for (int n = 0; n < 9; ++n) {
-        const bool ok = noff[n] >= 0;
         f32x4 xv;
-        { float a, b2; op_unpack2(ok ? raw0[n][0] : 0u, a, b2); xv[0] = a; xv[1] = b2; op_unpack2(ok ? raw0[n][1] : 0u, a, b2); xv[2] = a; xv[3] = b2; }
+        UNPACK4(xv, raw0[n], noff[n] >= 0);
         acc[n] += dN * xv;                 // tap a = 0: frame ti is the first input frame of output ti + 1
         acc[9 + n] += dC * xv;             // a = 1
         acc[18 + n] += dP * xv;            // a = 2
@@ -870,9 +854,8 @@ __global__ __launch_bounds__(PW_CQ * PW_LANES) void pool_wgrad_t_kernel(const op
       dP = dC; dC = dN; dN = d2;
 #pragma unroll
       for (int n = 0; n < 9; ++n) {
-        const bool ok = has1 && noff[n] >= 0;
         f32x4 xv;
-        { float a, b2; op_unpack2(ok ? raw1[n][0] : 0u, a, b2); xv[0] = a; xv[1] = b2; op_unpack2(ok ? raw1[n][1] : 0u, a, b2); xv[2] = a; xv[3] = b2; }
+        UNPACK4(xv, raw1[n], has1 && noff[n] >= 0);
         acc[n] += dN * xv;
         acc[9 + n] += dC * xv;
         acc[18 + n] += dP * xv;
@@ -880,18 +863,7 @@ __global__ __launch_bounds__(PW_CQ * PW_LANES) void pool_wgrad_t_kernel(const op
       dP = dC; dC = dN; dN = d3;
     }
   }
-  __syncthreads();
-  for (int k = 0; k < PW_LANES; ++k) {      // the 8 token lanes add their sums one after the other: a fixed order
-    if (tl == k) {
-#pragma unroll
-      for (int t = 0; t < 27; ++t)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) red[t][c0 + e] += acc[t][e];
-    }
-    __syncthreads();
-  }
-  float* mine = part + (long)blockIdx.x * (27 * HD);
-  for (int i = threadIdx.x; i < 27 * HD; i += PW_CQ * PW_LANES) mine[i] = red[i / HD][i % HD];
+  wgrad_flush(red, acc, tl, c0, part);
 }
 
 // dw[c][tap] += sum over workgroups of part[wg][tap][c] in a fixed order (deterministic): 16 outputs x 16 slices of
@@ -1074,7 +1046,7 @@ extern "C" int pvrl_im2col3d_bf16(const float* frames, int64_t B, int64_t Cin, i
     if (wgs > 8192) wgs = 8192;
     hipLaunchKernelGGL(im2col3d_rows_kernel, dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream, frames, (op_t*)out, g, (long)ldo);
   } else {
-    hipLaunchKernelGGL(im2col3d_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, frames, (op_t*)out, g, (long)ldo);
+    hipLaunchKernelGGL(im2col3d_kernel, dim3(grid_blocks(total)), dim3(256), 0, (hipStream_t)stream, frames, (op_t*)out, g, (long)ldo);
   }
   PVRL_LAUNCH_CHECK();
   return PVRL_OK;
@@ -1107,11 +1079,14 @@ extern "C" int pvrl_layernorm_g_fwd(const float* x, int64_t ldx, const float* ga
   return PVRL_OK;
 }
 
+// workgroups of ln_g_bwd_kernel = rows of its workspace of partials
+static long ln_g_bwd_blocks(int64_t M) {
+  const long blocks = (M + 3) / 4;
+  return blocks > 1024 ? 1024 : blocks < 1 ? 1 : blocks;
+}
+
 extern "C" int64_t pvrl_layernorm_g_bwd_workspace_bytes(int64_t M, int64_t C) {
-  int64_t blocks = (M + 3) / 4;
-  if (blocks > 1024) blocks = 1024;
-  if (blocks < 1) blocks = 1;
-  return blocks * 2 * C * (int64_t)sizeof(float);
+  return ln_g_bwd_blocks(M) * 2 * C * (int64_t)sizeof(float);
 }
 
 extern "C" int pvrl_layernorm_g_bwd(const void* dy, int64_t lddy, int dy_is_f32, const float* x, int64_t ldx,
@@ -1124,8 +1099,7 @@ extern "C" int pvrl_layernorm_g_bwd(const void* dy, int64_t lddy, int dy_is_f32,
       Cpad < C || Cpad > 64 * LNG_MAX || (dx16 && lddx16 < Cpad) ||
       workspace_bytes < pvrl_layernorm_g_bwd_workspace_bytes(M, C))
     return PVRL_EINVAL;
-  long blocks = (M + 3) / 4;
-  if (blocks > 1024) blocks = 1024;
+  const long blocks = ln_g_bwd_blocks(M);
   float* part = (float*)workspace;
   const int nj = (int)((Cpad + 63) / 64);
 #define LN_BWD(TD, NJ, RPI, RES)                                                                                         \
@@ -1167,18 +1141,11 @@ extern "C" int pvrl_mvit_pool_fwd(const void* qkv, int64_t ld, int64_t col0, int
   if (!qkv || !w || !gamma || !beta || !y || !conv_out || pool_geom(g, B, H, T, Hh, Ww, st, sh, sw, ld, col0)) return PVRL_EINVAL;
   const long ntok = (long)B * H * ((long)g.To * g.Ho * g.Wo + 1);
   if (ntok >= (1L << 27)) return PVRL_EINVAL;         // 16 lanes per token, 32-bit token arithmetic in the kernel
-  if (g.st == 1) {      // temporal stride 1 (every MViTv2 pooling operator): one 16-lane group per output column, sliding along t
-    const long ncol = (long)B * H * ((long)g.Ho * g.Wo + 1);
-    if (g.sh > 1 || g.sw > 1)
-      hipLaunchKernelGGL(pool_fwd_t_kernel<true>, dim3(grid_for(ncol * 16)), dim3(256), 0, (hipStream_t)stream, (const op_t*)qkv,
-                         g, w, gamma, beta, eps, (op_t*)y, (op_t*)conv_out);
-    else
-      hipLaunchKernelGGL(pool_fwd_t_kernel<false>, dim3(grid_for(ncol * 16)), dim3(256), 0, (hipStream_t)stream, (const op_t*)qkv,
-                         g, w, gamma, beta, eps, (op_t*)y, (op_t*)conv_out);
-  } else {
-    hipLaunchKernelGGL(pool_fwd_kernel, dim3(grid_for(ntok * 16)), dim3(256), 0, (hipStream_t)stream, (const op_t*)qkv, g,
-                       w, gamma, beta, eps, (op_t*)y, (op_t*)conv_out);
-  }
+  // temporal stride 1 (every MViTv2 pooling operator): one 16-lane group per output column, sliding along t; else one per token
+  const long ncol = (long)B * H * ((long)g.Ho * g.Wo + 1);
+  const auto kernel = g.st != 1 ? pool_fwd_kernel : (g.sh > 1 || g.sw > 1) ? pool_fwd_t_kernel<true> : pool_fwd_t_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(grid_blocks((g.st == 1 ? ncol : ntok) * 16)), dim3(256), 0, (hipStream_t)stream, (const op_t*)qkv,
+                     g, w, gamma, beta, eps, (op_t*)y, (op_t*)conv_out);
   PVRL_LAUNCH_CHECK();
   return PVRL_OK;
 }
@@ -1211,18 +1178,13 @@ extern "C" int pvrl_mvit_pool_bwd(const void* dy, const void* conv_out, const vo
   hipLaunchKernelGGL(partials_add_kernel, dim3((2 * HD + PADD_OUT - 1) / PADD_OUT), dim3(256), 0, s, (const float*)lnpart, (int)blocks,
                      2 * HD, dgamma, dbeta, HD);
   PVRL_LAUNCH_CHECK();
-  {
-    const dim3 dg(grid_for(nin * 16)), db(256);
-    const int S = (st == 1 && sh == sw && (sh == 1 || sh == 2 || sh == 4 || sh == 8)) ? (int)sh : 0;
-#define DGRAD_T(DD, SS) hipLaunchKernelGGL((pool_dgrad_t_kernel<DD, SS>), dim3(grid_for((long)B * H * Hh * Ww * 16)), db, 0, s, \
-                                           (const op_t*)dc_scratch, g, w, (op_t*)dqkv)
-    if (st == 1 && sh == 1 && sw == 1) DGRAD_T(true, 1);   // temporal stride 1: one 16-lane group per input column, sliding along t
-    else if (st == 1 && S == 2) DGRAD_T(false, 2);
-    else if (st == 1 && S == 4) DGRAD_T(false, 4);
-    else if (st == 1 && S == 8) DGRAD_T(false, 8);
-    else if (st == 1) DGRAD_T(false, 0);
-#undef DGRAD_T
-    else hipLaunchKernelGGL(pool_dgrad_kernel, dg, db, 0, s, (const op_t*)dc_scratch, g, w, (op_t*)dqkv);   // temporal stride > 1
+  if (st == 1) {       // one 16-lane group per input column, sliding along t; the spatial stride a compile-time constant where it can be
+    const int S = sh == sw ? (int)sh : 0;
+    const auto kernel = S == 1 ? pool_dgrad_t_kernel<true, 1> : S == 2 ? pool_dgrad_t_kernel<false, 2> :
+                        S == 4 ? pool_dgrad_t_kernel<false, 4> : S == 8 ? pool_dgrad_t_kernel<false, 8> : pool_dgrad_t_kernel<false, 0>;
+    hipLaunchKernelGGL(kernel, dim3(grid_blocks((long)B * H * Hh * Ww * 16)), dim3(256), 0, s, (const op_t*)dc_scratch, g, w, (op_t*)dqkv);
+  } else {             // one 16-lane group per input token
+    hipLaunchKernelGGL(pool_dgrad_kernel, dim3(grid_blocks(nin * 16)), dim3(256), 0, s, (const op_t*)dc_scratch, g, w, (op_t*)dqkv);
   }
   PVRL_LAUNCH_CHECK();
   long wb = (B * H * Lo + PW_LANES * 16 - 1) / (PW_LANES * 16);      // >= 16 tokens per lane: 2,592 global atomics per block
@@ -1263,7 +1225,7 @@ extern "C" int pvrl_mvit_maxpool_fwd(const float* x, int64_t ldi, int64_t B, int
   if (!x || !y || maxpool_geom(g, B, T, H, W, s, C, ldi, ldo) || (argmax && s > MAXPOOL_ARGMAX_MAX_S)) return PVRL_EINVAL;
   const long total = ((long)B * T * g.Ho * g.Wo + B) * (C >> 2);
   if (total >= (1L << 31) - (1L << 24)) return PVRL_EINVAL;          // 32-bit index arithmetic in the kernel
-  hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, g, y,
+  hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(grid_blocks(total)), dim3(256), 0, (hipStream_t)stream, x, g, y,
                      (unsigned char*)argmax);
   PVRL_LAUNCH_CHECK();
   return PVRL_OK;
@@ -1278,7 +1240,7 @@ extern "C" int pvrl_mvit_maxpool_bwd(const float* x, int64_t ldi, const float* d
   //  across replays; nothing on a captured path uses hipMemset* any more.)
   const long total = ((long)B * T * H * W + B) * (C >> 2);
   if (total >= (1L << 31) - (1L << 24)) return PVRL_EINVAL;          // 32-bit index arithmetic in the kernel
-  hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, dy, g, dx,
+  hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_blocks(total)), dim3(256), 0, (hipStream_t)stream, x, dy, g, dx,
                      (const unsigned char*)argmax);
   PVRL_LAUNCH_CHECK();
   return PVRL_OK;
@@ -1288,7 +1250,7 @@ extern "C" int pvrl_copy2d_f32(const float* in, int64_t ldi, float* out, int64_t
                                void* stream) {
   if (R <= 0 || C <= 0) return PVRL_OK;
   if (!in || !out || ldi < C || ldo < C) return PVRL_EINVAL;
-  hipLaunchKernelGGL(copy2d_kernel, dim3(grid_for(R * C)), dim3(256), 0, (hipStream_t)stream, in, (long)ldi, out,
+  hipLaunchKernelGGL(copy2d_kernel, dim3(grid_blocks(R * C)), dim3(256), 0, (hipStream_t)stream, in, (long)ldi, out,
                      (long)ldo, (long)R, (int)C, beta);
   PVRL_LAUNCH_CHECK();
   return PVRL_OK;

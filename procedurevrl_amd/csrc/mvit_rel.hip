@@ -19,13 +19,6 @@ namespace {
 constexpr int HD = PB_D;          // 96
 constexpr int REL_KMAX = 16;      // k_h, k_w, k_t <= 16: one MFMA row block
 
-inline unsigned grid_for(long total, int per_block = 256) {
-  long b = (total + per_block - 1) / per_block;
-  if (b < 1) b = 1;
-  if (b > 65535L * 16) b = 65535L * 16;
-  return (unsigned)b;
-}
-
 struct RelGeom {
   int BH, qt, qh, qw, kt, kh, kw;   // J = kh + kw + kt columns: [0,kh) height, [kh,kh+kw) width, then time
 };
@@ -401,7 +394,7 @@ extern "C" int pvrl_mvit_rel_bwd(const float* drel, const void* Q, void* dQ, int
     hipLaunchKernelGGL((rel_bwd_q_kernel<12, true>), dim3(grid), dim3(1024), 0, s, drel, g, Rh, Rw, Rt, idx_h, idx_w, idx_t,
                        (int)nrows_h, (int)nrows_w, (int)nrows_t, (op_t*)dQ);
   } else {
-    hipLaunchKernelGGL((rel_bwd_q_kernel<12, false>), dim3(grid_for(nthr)), dim3(256), 0, s, drel, g, Rh, Rw, Rt, idx_h, idx_w, idx_t,
+    hipLaunchKernelGGL((rel_bwd_q_kernel<12, false>), dim3(grid_blocks(nthr)), dim3(256), 0, s, drel, g, Rh, Rw, Rt, idx_h, idx_w, idx_t,
                        (int)nrows_h, (int)nrows_w, (int)nrows_t, (op_t*)dQ);
   }
   PVRL_LAUNCH_CHECK();

@@ -33,7 +33,7 @@ attention_pool
   ln_bwd, ln_bwd.loop when B H (Lo + 1) > 32,768 (the grid-stride loop of pool_ln_bwd_kernel).  pool_dgrad_kernel has run-time strides
   only: a compile-time spatial stride S > 0 exists only for st = 1, and st = 1 always takes a dgrad_t form, so pool_dgrad_kernel<S > 0>
   could never be reached from pvrl_mvit_pool_bwd and is gone from mvit.hip.  NOT reachable at test size and left to the end-to-end checks
-  (mvit_checks.check_mvit_timed_config_train_step): the `grid_for` cap (1,048,560 workgroups) and PW_MAX_WG (2,048 workgroups of the
+  (mvit_checks.check_mvit_timed_config_train_step): the `grid_blocks` cap (1,048,560 workgroups) and PW_MAX_WG (2,048 workgroups of the
   weight gradient = 262,144 output tokens).
 max-pool skip
   Reference mvit_oracle.pool_skip in fp64; both outputs BIT-EXACT (the forward selects; dy is drawn from multiples of 2^-6 with
@@ -127,7 +127,7 @@ def pool_names(B, H, thw, stride):
 
 
 def fwd_grid(c):
-    """workgroups of the forward launch (grid_for(16 lanes per column / token, 256 threads)): the XCD launch-order remap sees it"""
+    """workgroups of the forward launch (grid_blocks(16 lanes per column / token, 256 threads)): the XCD launch-order remap sees it"""
     o = out_thw(c.thw, c.stride)
     n = c.B * c.H * ((o[1] * o[2] if c.stride[0] == 1 else o[0] * o[1] * o[2]) + 1)
     return max(1, -(-n * 16 // 256))
