@@ -175,6 +175,20 @@ int pvrl_layernorm_bwd_split(const void* dy, int64_t lddy, int dy_is_f32, const 
                              float* dbeta, void* workspace, int64_t workspace_bytes, int64_t M, int64_t C, void* dxs_bf16,
                              int64_t ldxs, const float* dxs_scale, int64_t dxs_rows, float* dxsum, const float* gscale,
                              float* nonfinite, void* stream);
+/* The encoder's FINAL norm over every token (VisionTransformer.forward_features(x, cls=False), vit.py:418-423): the fp32 side -- y in
+ * the forward, dy in the backward -- is the reference's token tensor [B, 1 + P, C] as a matrix of M = B (P + 1) rows, P =
+ * rows_per_clip (N T; N for `space_only`), while x, mean / rstd, dx_in / dx_out and dxs keep the engine's rows: R = B P patch rows
+ * (b, n, t), then the B cls rows.  Engine row m < R is token row m + m / P + 1, cls row R + b is token row b (P + 1).  x->rows16 is R
+ * (split stream) or 0 (all fp32).  Everything else as _fwd_split (fp32 output) / _bwd_split (fp32 dy), the deferred reduce
+ * (dgamma = dbeta = null, then pvrl_layernorm_bwd_reduce_batched with the same M, C) included; dxs_rows <= M counts engine rows.
+ * PVRL_EINVAL before any launch: C not 768 / 1024, rows_per_clip < 1, M no multiple of P + 1, a split elsewhere than at R. */
+int pvrl_layernorm_fwd_tokens(const pvrl_rows* x, const float* gamma, const float* beta, float eps, float* y, int64_t ldy, float* mean,
+                              float* rstd, int64_t M, int64_t C, int64_t rows_per_clip, void* stream);
+int pvrl_layernorm_bwd_tokens(const float* dy, int64_t lddy, const pvrl_rows* x, const float* mean, const float* rstd,
+                              const float* gamma, const pvrl_rows* dx_in, const pvrl_rows* dx_out, float beta_acc, float* dgamma,
+                              float* dbeta, void* workspace, int64_t workspace_bytes, int64_t M, int64_t C, int64_t rows_per_clip,
+                              void* dxs_bf16, int64_t ldxs, const float* dxs_scale, int64_t dxs_rows, float* dxsum,
+                              const float* gscale, float* nonfinite, void* stream);
 
 /* pvrl_layernorm_bwd with dgamma = dbeta = null leaves its per-workgroup partial sums in `workspace` (the caller keeps that workspace
  * to itself) instead of reducing them; this entry point then reduces the partials of MANY LayerNorms in one launch -- an encoder backward

@@ -54,12 +54,23 @@ template <> struct Part<false> {
   static __device__ __forceinline__ T* row(const Rows& r, int m) { return r.hi ? r.hi + (long)(m - r.rows16) * r.ldhi : nullptr; }
 };
 
+// TOKEN row map (forward_features(cls=False)): the fp32 side of a final-norm launch -- y in the forward, dy in the backward -- is the
+// reference's [B, 1 + P, C] token tensor as a [B (P + 1), C] matrix, while x / dx keep the engine's order (R = B P patch rows, then
+// the B cls rows).  Engine row m < R lies at token row m + m / P + 1, cls row R + b at b (P + 1): a whole row moves, so every access
+// stays the 16-byte vector access it was, and a clip seam inside a workgroup's rows is nothing special.  TOK is a compile-time switch
+// of the row kernels below; the instantiations with TOK off take the row as it is.
+struct TokMap { int P, R; };
+template <bool TOK> __device__ __forceinline__ long tok_row(const TokMap& t, int m) {
+  if constexpr (TOK) return m < t.R ? (long)m + m / t.P + 1 : (long)(m - t.R) * (t.P + 1);
+  else return m;
+}
+
 // RPW rows per wave, all their loads in flight together: a 16-bit row is 1.5 KB, and one of them per wave (8 B per lane and load
 // instruction) does not keep enough bytes in flight to reach the HBM rate -- 33.6 us = 4.6 TB/s against 5.9 for fp32 rows (round 6).
-template <int C, typename TOut, bool LO, int RPW>
+template <int C, typename TOut, bool LO, int RPW, bool TOK = false>
 __device__ __forceinline__ void ln_fwd_rows(const Rows& x, int row, int nrow, int lane, const float* __restrict__ gamma,
                                             const float* __restrict__ beta, float eps, TOut* __restrict__ y, long ldy,
-                                            float* __restrict__ mean, float* __restrict__ rstd) {
+                                            float* __restrict__ mean, float* __restrict__ rstd, const TokMap tok = TokMap{1, 0}) {
   constexpr int NV = C / 256;
   typedef typename Part<LO>::T TX;
   f32x4 v[RPW][NV];
@@ -92,7 +103,7 @@ __device__ __forceinline__ void ln_fwd_rows(const Rows& x, int row, int nrow, in
         if (mean) mean[row + r] = mu;
         if (rstd) rstd[row + r] = rs;
       }
-      TOut* yr = y + (long)(row + r) * ldy;
+      TOut* yr = y + tok_row<TOK>(tok, row + r) * ldy;
 #pragma unroll
       for (int j = 0; j < NV; ++j) {
         f32x4 o;
@@ -123,6 +134,25 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const Rows x, const float* 
   }
 }
 
+// ... with the token row map on y (fp32): the same rows, stored at their token rows
+template <int C>
+__global__ __launch_bounds__(256) void ln_fwd_tokens_kernel(const Rows x, const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta, float eps, float* __restrict__ y,
+                                                            long ldy, float* __restrict__ mean, float* __restrict__ rstd,
+                                                            int M, int nb_lo, const TokMap tok) {
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if ((int)blockIdx.x < nb_lo) {
+    const int row = ((int)blockIdx.x * 4 + wave) * LN_FWD_RPW16;
+    if (row >= x.rows16) return;
+    ln_fwd_rows<C, float, true, LN_FWD_RPW16, true>(x, row, min(LN_FWD_RPW16, x.rows16 - row), lane, gamma, beta, eps, y, ldy, mean,
+                                                    rstd, tok);
+  } else {
+    const int row = x.rows16 + ((int)blockIdx.x - nb_lo) * 4 + wave;
+    if (row >= M) return;
+    ln_fwd_rows<C, float, false, 1, true>(x, row, 1, lane, gamma, beta, eps, y, ldy, mean, rstd, tok);
+  }
+}
+
 // workgroups of a backward launch over M rows: one more than the rows need, so that a split matrix always has a workgroup for each part
 constexpr int LN_BWD_MAX_BLOCKS = 512;
 inline int ln_bwd_nblk(long M) {
@@ -142,13 +172,13 @@ inline int ln_bwd_nblk_hi(long M, long rows16) {
 // the loads: behind `ptr ? load : 0` every load waits for its own round trip).
 // RPW rows per wave and iteration (rows row, row + 4 nb, ...), every load of all of them issued before the first wait: two on the
 // 16-bit part, where one row's nine 8-byte loads per lane keep too few bytes in flight (one row: 83 us = 4.6 TB/s at M = 50k).
-template <int C, typename TDy, bool LO, bool HAS_IN, int RPW>
+template <int C, typename TDy, bool LO, bool HAS_IN, int RPW, bool TOK>
 __device__ __forceinline__ void ln_bwd_rows(int row0, int row1, int bid, int nb, int lane, int wave, const TDy* __restrict__ dy,
                                             long lddy, const Rows& x, const float* __restrict__ mean,
                                             const float* __restrict__ rstd, const Rows& dx_in, const Rows& dx_out,
                                             op_t* __restrict__ dxs, long ldxs, const float* __restrict__ dxs_scale, int dxs_rows,
                                             int want_sum, const f32x4 (&g)[C / 256], f32x4 (&dg)[C / 256], f32x4 (&db)[C / 256],
-                                            f32x4 (&ds)[C / 256]) {
+                                            f32x4 (&ds)[C / 256], const TokMap& tok) {
   constexpr int NV = C / 256;
   typedef typename Part<LO>::T TX;
   const int step = nb * 4;
@@ -177,7 +207,7 @@ __device__ __forceinline__ void ln_bwd_rows(int row0, int row1, int bid, int nb,
 #pragma unroll
       for (int j = 0; j < NV; ++j) {
         xv[r][j] = Vec4IO<TX>::load(xr + 4 * lane + 256 * j);
-        dv[r][j] = Vec4IO<TDy>::load(dy + (long)row * lddy + 4 * lane + 256 * j);
+        dv[r][j] = Vec4IO<TDy>::load(dy + tok_row<TOK>(tok, row) * lddy + 4 * lane + 256 * j);
       }
     }
 #pragma unroll
@@ -221,16 +251,16 @@ __device__ __forceinline__ void ln_bwd_rows(int row0, int row1, int bid, int nb,
 
 constexpr int LN_BWD_RPW16 = 2;      // rows per wave and iteration on the 16-bit part
 
-template <int C, typename TDy>
-__global__ __launch_bounds__(256) void ln_bwd_kernel(const TDy* __restrict__ dy, long lddy, const Rows x,
-                                                     const float* __restrict__ mean,
-                                                     const float* __restrict__ rstd, const float* __restrict__ gamma,
-                                                     const Rows dx_in, const Rows dx_out,
-                                                     float* __restrict__ part, int M, op_t* __restrict__ dxs,
-                                                     long ldxs, const float* __restrict__ dxs_scale, int dxs_rows,
-                                                     int want_sum, int nb_hi) {
+// the backward's workgroup: its share of the rows, then its partial sums (`red`: the workgroup's LDS)
+template <int C, typename TDy, bool TOK>
+__device__ __forceinline__ void ln_bwd_block(float (&red)[4][2][C], const TDy* __restrict__ dy, long lddy, const Rows& x,
+                                             const float* __restrict__ mean,
+                                             const float* __restrict__ rstd, const float* __restrict__ gamma,
+                                             const Rows& dx_in, const Rows& dx_out,
+                                             float* __restrict__ part, int M, op_t* __restrict__ dxs,
+                                             long ldxs, const float* __restrict__ dxs_scale, int dxs_rows,
+                                             int want_sum, int nb_hi, const TokMap tok) {
   constexpr int NV = C / 256;
-  __shared__ float red[4][2][C];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int pstride = (2 + want_sum) * C;       // floats per workgroup in `part`: dgamma | dbeta | (column sums of dx_out)
   f32x4 g[NV], dg[NV], db[NV], ds[NV];
@@ -243,8 +273,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const TDy* __restrict__ dy,
   }
   const int nb_lo = (int)gridDim.x - nb_hi;
 #define LN_ROWS(LO_, IN_, r0, r1, b, n)                                                                                          \
-  ln_bwd_rows<C, TDy, LO_, IN_, (LO_ ? LN_BWD_RPW16 : 1)>(r0, r1, b, n, lane, wave, dy, lddy, x, mean, rstd, dx_in, dx_out, dxs, ldxs, \
-                                                          dxs_scale, dxs_rows, want_sum, g, dg, db, ds)
+  ln_bwd_rows<C, TDy, LO_, IN_, (LO_ ? LN_BWD_RPW16 : 1), TOK>(r0, r1, b, n, lane, wave, dy, lddy, x, mean, rstd, dx_in, dx_out, dxs, \
+                                                               ldxs, dxs_scale, dxs_rows, want_sum, g, dg, db, ds, tok)
   if ((int)blockIdx.x < nb_lo) {
     if (dx_in.lo) LN_ROWS(true, true, 0, x.rows16, (int)blockIdx.x, nb_lo);
     else LN_ROWS(true, false, 0, x.rows16, (int)blockIdx.x, nb_lo);
@@ -279,6 +309,33 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const TDy* __restrict__ dy,
     for (int c = threadIdx.x; c < C; c += 256)
       part[(long)blockIdx.x * pstride + 2 * C + c] = red[0][0][c] + red[1][0][c] + red[2][0][c] + red[3][0][c];
   }
+}
+
+template <int C, typename TDy>
+__global__ __launch_bounds__(256) void ln_bwd_kernel(const TDy* __restrict__ dy, long lddy, const Rows x,
+                                                     const float* __restrict__ mean,
+                                                     const float* __restrict__ rstd, const float* __restrict__ gamma,
+                                                     const Rows dx_in, const Rows dx_out,
+                                                     float* __restrict__ part, int M, op_t* __restrict__ dxs,
+                                                     long ldxs, const float* __restrict__ dxs_scale, int dxs_rows,
+                                                     int want_sum, int nb_hi) {
+  __shared__ float red[4][2][C];
+  ln_bwd_block<C, TDy, false>(red, dy, lddy, x, mean, rstd, gamma, dx_in, dx_out, part, M, dxs, ldxs, dxs_scale, dxs_rows, want_sum,
+                              nb_hi, TokMap{1, 0});
+}
+
+// ... with the token row map on dy (fp32 [B (P + 1), C]): x, the statistics, dx and dxs keep the engine's rows
+template <int C>
+__global__ __launch_bounds__(256) void ln_bwd_tokens_kernel(const float* __restrict__ dy, long lddy, const Rows x,
+                                                            const float* __restrict__ mean,
+                                                            const float* __restrict__ rstd, const float* __restrict__ gamma,
+                                                            const Rows dx_in, const Rows dx_out,
+                                                            float* __restrict__ part, int M, op_t* __restrict__ dxs,
+                                                            long ldxs, const float* __restrict__ dxs_scale, int dxs_rows,
+                                                            int want_sum, int nb_hi, const TokMap tok) {
+  __shared__ float red[4][2][C];
+  ln_bwd_block<C, float, true>(red, dy, lddy, x, mean, rstd, gamma, dx_in, dx_out, part, M, dxs, ldxs, dxs_scale, dxs_rows, want_sum,
+                               nb_hi, tok);
 }
 
 // out[j] = beta*out[j] + gscale * sum_b part[b][j]   (j over 2*C: dgamma then dbeta); gscale / nonfinite as in gemm_tn_core.h: the
@@ -355,9 +412,21 @@ __global__ __launch_bounds__(256) void colpart_reduce_batched_kernel(LnReduceBat
 
 }  // namespace
 
-extern "C" int pvrl_layernorm_fwd_split(const void* x16, int64_t ldx16, int64_t rows16, const float* x, int64_t ldx,
-                                        const float* gamma, const float* beta, float eps, void* y, int64_t ldy, int out_is_f32,
-                                        float* mean, float* rstd, int64_t M, int64_t C, void* stream) {
+namespace {
+// the token row map of M = B (P + 1) rows, P = rows_per_clip; a split matrix must be split at R = B P (the patch rows 16-bit, the
+// cls rows fp32) or not at all
+bool tok_map(int64_t M, int64_t rows_per_clip, int64_t rows16, TokMap* tok) {
+  if (rows_per_clip < 1 || M > 0x7fffffffL || M % (rows_per_clip + 1)) return false;
+  const int64_t R = M / (rows_per_clip + 1) * rows_per_clip;
+  if (rows16 != 0 && rows16 != R) return false;
+  *tok = TokMap{(int)rows_per_clip, (int)R};
+  return true;
+}
+
+// rows_per_clip = 0: no row map (pvrl_layernorm_fwd_split); otherwise y is the fp32 token matrix
+int ln_fwd_launch(const void* x16, int64_t ldx16, int64_t rows16, const float* x, int64_t ldx, const float* gamma, const float* beta,
+                  float eps, void* y, int64_t ldy, int out_is_f32, float* mean, float* rstd, int64_t M, int64_t C,
+                  int64_t rows_per_clip, void* stream) {
   if (M <= 0) return PVRL_OK;
   if (rows16 < 0 || rows16 > M || (rows16 > 0 && (!x16 || (ldx16 % 4))) || (rows16 < M && (!x || (ldx % 4)))) return PVRL_EINVAL;
   if (!gamma || !beta || !y || (ldy % 4)) return PVRL_EINVAL;
@@ -365,6 +434,17 @@ extern "C" int pvrl_layernorm_fwd_split(const void* x16, int64_t ldx16, int64_t 
   const int nb_lo = (int)cdiv(rows16, 4 * LN_FWD_RPW16);
   const dim3 grid((unsigned)(nb_lo + cdiv(M - rows16, 4))), blk(256);
   const Rows xr = {(op_t*)x16, (long)ldx16, (float*)x, (long)ldx, (int)rows16};
+  if (rows_per_clip) {
+    TokMap tok;
+    if ((C != 768 && C != 1024) || ldy < C || !tok_map(M, rows_per_clip, rows16, &tok)) return PVRL_EINVAL;
+#define LN_FWD_TOK(CC)                                                                                               \
+  hipLaunchKernelGGL((ln_fwd_tokens_kernel<CC>), grid, blk, 0, s, xr, gamma, beta, eps, (float*)y, (long)ldy, mean, rstd, \
+                     (int)M, nb_lo, tok);
+    if (C == 768) { LN_FWD_TOK(768) } else { LN_FWD_TOK(1024) }
+#undef LN_FWD_TOK
+    PVRL_LAUNCH_CHECK();
+    return PVRL_OK;
+  }
 #define LN_FWD(CC)                                                                                                  \
   if (out_is_f32)                                                                                                   \
     hipLaunchKernelGGL((ln_fwd_kernel<CC, float>), grid, blk, 0, s, xr, gamma, beta, eps, (float*)y,                 \
@@ -376,6 +456,20 @@ extern "C" int pvrl_layernorm_fwd_split(const void* x16, int64_t ldx16, int64_t 
 #undef LN_FWD
   PVRL_LAUNCH_CHECK();
   return PVRL_OK;
+}
+}  // namespace
+
+extern "C" int pvrl_layernorm_fwd_split(const void* x16, int64_t ldx16, int64_t rows16, const float* x, int64_t ldx,
+                                        const float* gamma, const float* beta, float eps, void* y, int64_t ldy, int out_is_f32,
+                                        float* mean, float* rstd, int64_t M, int64_t C, void* stream) {
+  return ln_fwd_launch(x16, ldx16, rows16, x, ldx, gamma, beta, eps, y, ldy, out_is_f32, mean, rstd, M, C, 0, stream);
+}
+
+extern "C" int pvrl_layernorm_fwd_tokens(const pvrl_rows* x, const float* gamma, const float* beta, float eps, float* y, int64_t ldy,
+                                         float* mean, float* rstd, int64_t M, int64_t C, int64_t rows_per_clip, void* stream) {
+  if (!x || rows_per_clip < 1 || (C != 768 && C != 1024)) return PVRL_EINVAL;
+  return ln_fwd_launch(x->lo, x->ldlo, x->rows16, (const float*)x->hi, x->ldhi, gamma, beta, eps, y, ldy, 1, mean, rstd, M, C,
+                       rows_per_clip, stream);
 }
 
 extern "C" int pvrl_layernorm_fwd(const float* x, int64_t ldx, const float* gamma, const float* beta, float eps,
@@ -389,11 +483,13 @@ extern "C" int64_t pvrl_layernorm_bwd_workspace_bytes(int64_t M, int64_t C) {
   return (int64_t)ln_bwd_nblk(M > 0 ? M : 1) * 3 * C * (int64_t)sizeof(float);   // dgamma | dbeta | optional column sums of dx_out
 }
 
-extern "C" int pvrl_layernorm_bwd_split(const void* dy, int64_t lddy, int dy_is_f32, const pvrl_rows* x, const float* mean,
-                                        const float* rstd, const float* gamma, const pvrl_rows* dx_in, const pvrl_rows* dx_out,
-                                        float beta_acc, float* dgamma, float* dbeta, void* workspace, int64_t workspace_bytes,
-                                        int64_t M, int64_t C, void* dxs_bf16, int64_t ldxs, const float* dxs_scale,
-                                        int64_t dxs_rows, float* dxsum, const float* gscale, float* nonfinite, void* stream) {
+namespace {
+// rows_per_clip = 0: no row map (pvrl_layernorm_bwd_split); otherwise dy is the fp32 token matrix
+int ln_bwd_launch(const void* dy, int64_t lddy, int dy_is_f32, const pvrl_rows* x, const float* mean,
+                  const float* rstd, const float* gamma, const pvrl_rows* dx_in, const pvrl_rows* dx_out,
+                  float beta_acc, float* dgamma, float* dbeta, void* workspace, int64_t workspace_bytes,
+                  int64_t M, int64_t C, void* dxs_bf16, int64_t ldxs, const float* dxs_scale,
+                  int64_t dxs_rows, float* dxsum, const float* gscale, float* nonfinite, int64_t rows_per_clip, void* stream) {
   if (M <= 0) return PVRL_OK;
   if (!dy || !x || !mean || !rstd || !gamma || !dx_out || (!dgamma != !dbeta) || !workspace || (lddy % 4)) return PVRL_EINVAL;
   auto bad = [&](const pvrl_rows* r, bool need) {       // every part that holds rows must be there (x) / may be null (dx_in: zeros)
@@ -415,6 +511,15 @@ extern "C" int pvrl_layernorm_bwd_split(const void* dy, int64_t lddy, int dy_is_
   float* part = (float*)workspace;
   const int want_sum = dxsum ? 1 : 0;
   const int pstride = (2 + want_sum) * (int)C;
+  if (rows_per_clip) {
+    TokMap tok;
+    if ((C != 768 && C != 1024) || !dy_is_f32 || lddy < C || dxs_rows > M || !tok_map(M, rows_per_clip, xr.rows16, &tok)) return PVRL_EINVAL;
+#define LN_BWD_TOK(CC)                                                                                                 \
+  hipLaunchKernelGGL((ln_bwd_tokens_kernel<CC>), dim3(nblk), dim3(256), 0, s, (const float*)dy, (long)lddy, xr, mean, rstd, \
+                     gamma, dxi, dxo, part, (int)M, (op_t*)dxs_bf16, (long)ldxs, dxs_scale, (int)dxs_rows, want_sum, nb_hi, tok);
+    if (C == 768) { LN_BWD_TOK(768) } else { LN_BWD_TOK(1024) }
+#undef LN_BWD_TOK
+  } else {
 #define LN_BWD(CC)                                                                                                   \
   if (dy_is_f32)                                                                                                     \
     hipLaunchKernelGGL((ln_bwd_kernel<CC, float>), dim3(nblk), dim3(256), 0, s, (const float*)dy, (long)lddy, xr,     \
@@ -426,6 +531,7 @@ extern "C" int pvrl_layernorm_bwd_split(const void* dy, int64_t lddy, int dy_is_
                        (op_t*)dxs_bf16, (long)ldxs, dxs_scale, (int)dxs_rows, want_sum, nb_hi);
   if (C == 768) { LN_BWD(768) } else if (C == 1024) { LN_BWD(1024) } else if (C == 512) { LN_BWD(512) } else return PVRL_EINVAL;
 #undef LN_BWD
+  }
   PVRL_LAUNCH_CHECK();
   if (!dgamma) return PVRL_OK;       // deferred: the partials stay in `workspace` for pvrl_layernorm_bwd_reduce_batched
   hipLaunchKernelGGL(colpart_reduce_kernel, dim3((unsigned)cdiv(2 * C, 16)), dim3(256), 0, s, part, nblk,
@@ -437,6 +543,26 @@ extern "C" int pvrl_layernorm_bwd_split(const void* dy, int64_t lddy, int dy_is_
     PVRL_LAUNCH_CHECK();
   }
   return PVRL_OK;
+}
+}  // namespace
+
+extern "C" int pvrl_layernorm_bwd_split(const void* dy, int64_t lddy, int dy_is_f32, const pvrl_rows* x, const float* mean,
+                                        const float* rstd, const float* gamma, const pvrl_rows* dx_in, const pvrl_rows* dx_out,
+                                        float beta_acc, float* dgamma, float* dbeta, void* workspace, int64_t workspace_bytes,
+                                        int64_t M, int64_t C, void* dxs_bf16, int64_t ldxs, const float* dxs_scale,
+                                        int64_t dxs_rows, float* dxsum, const float* gscale, float* nonfinite, void* stream) {
+  return ln_bwd_launch(dy, lddy, dy_is_f32, x, mean, rstd, gamma, dx_in, dx_out, beta_acc, dgamma, dbeta, workspace, workspace_bytes,
+                       M, C, dxs_bf16, ldxs, dxs_scale, dxs_rows, dxsum, gscale, nonfinite, 0, stream);
+}
+
+extern "C" int pvrl_layernorm_bwd_tokens(const float* dy, int64_t lddy, const pvrl_rows* x, const float* mean, const float* rstd,
+                                         const float* gamma, const pvrl_rows* dx_in, const pvrl_rows* dx_out, float beta_acc,
+                                         float* dgamma, float* dbeta, void* workspace, int64_t workspace_bytes, int64_t M, int64_t C,
+                                         int64_t rows_per_clip, void* dxs_bf16, int64_t ldxs, const float* dxs_scale, int64_t dxs_rows,
+                                         float* dxsum, const float* gscale, float* nonfinite, void* stream) {
+  if (rows_per_clip < 1 || (C != 768 && C != 1024)) return PVRL_EINVAL;
+  return ln_bwd_launch(dy, lddy, 1, x, mean, rstd, gamma, dx_in, dx_out, beta_acc, dgamma, dbeta, workspace, workspace_bytes, M, C,
+                       dxs_bf16, ldxs, dxs_scale, dxs_rows, dxsum, gscale, nonfinite, rows_per_clip, stream);
 }
 
 extern "C" int pvrl_layernorm_bwd(const void* dy, int64_t lddy, int dy_is_f32, const float* x, int64_t ldx,

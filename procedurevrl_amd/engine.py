@@ -139,15 +139,17 @@ class EncoderEngine(GraphReplay):
         self._keep = None
         self._graph_init()            # HIP-graph replay of the step (GraphReplay)
         self._refreshed = False
+        self._tok = False             # the running forward() returns every token (part of the graph key)
         # the sizes the kernels serve, ViT-B (768, 12) and ViT-L (1024, 16): a clear error here for any other pair
         ops.check_encoder_width(self.C, self.H)
         # the geometry the model was built for (DATA.TRAIN_CROP_SIZE, DATA.NUM_FRAMES) against the attention kernels' limits: a clear
         # error here instead of PVRL_EINVAL from inside the first block (a forward checks its input's own geometry again)
         self._check_geometry(model.patch_embed.num_patches, model.time_embed.shape[1] if hasattr(model, "time_embed") else 1)
 
-    def _check_geometry(self, N, T, **keys):
+    def _check_geometry(self, N, T, prune=True, **keys):
+        """`prune` False: a call whose last block runs unpruned whatever the switches say (forward(tokens=True))"""
         scheme = getattr(self.m, "attention_type", "divided_space_time")
-        ops.check_attn_geometry(N, T, scheme, self.prune_last and self.prune_attn, **keys)
+        ops.check_attn_geometry(N, T, scheme, prune and self.prune_last and self.prune_attn, **keys)
 
     # ------------------------------------------------------------------ weights
     def _weight(self, p, need_t=True):
@@ -383,18 +385,24 @@ class EncoderEngine(GraphReplay):
         return pos.contiguous(), tim.contiguous()
 
     # ------------------------------------------------------------------ forward
-    def forward(self, frames, training, droppath=None, save=True):
+    def forward(self, frames, training, droppath=None, save=True, tokens=False):
         """frames fp32 [B, 3, T, H, W] on the GPU (or transform.DecodedClips) -> (feat fp32 [B, C] = norm(x)[:, 0]).
         `droppath`: optional list (per block) of dicts from expand_droppath, to pin the RNG draws.
+        `tokens`: norm(x) of every token instead, fp32 [B, 1 + N*T, C] in the reference's order (forward_features(cls=False),
+        vit.py:418-423; [B, 1 + N, C] for `space_only`): the last block then runs unpruned and the final norm covers all rows.
         With `use_graphs` the launch sequence of a (shape, mode) is captured once into a HIP graph and replayed."""
-        if self.use_graphs and droppath is None and isinstance(frames, torch.Tensor) and frames.is_cuda:
-            return self._graph_forward(frames, training, save)
-        self._gkey = None
-        return self._forward(frames, training, droppath, save)
+        self._tok = bool(tokens)            # (read by _graph_key / _eager_forward: the replay core passes frames, training, save)
+        try:
+            if self.use_graphs and droppath is None and isinstance(frames, torch.Tensor) and frames.is_cuda:
+                return self._graph_forward(frames, training, save)
+            self._gkey = None
+            return self._forward(frames, training, droppath, save, tokens=self._tok)
+        finally:
+            self._tok = False
 
-    def _forward(self, frames, training, droppath=None, save=True):
+    def _forward(self, frames, training, droppath=None, save=True, tokens=False):
         # the input's own geometry (a test crop may differ from the model's) against the kernels' limits, before the first launch
-        self._check_geometry((frames.shape[3] // 16) * (frames.shape[4] // 16), frames.shape[2],
+        self._check_geometry((frames.shape[3] // 16) * (frames.shape[4] // 16), frames.shape[2], prune=not tokens,
                              crop_key="input crop (DATA.TRAIN_CROP_SIZE / DATA.TEST_CROP_SIZE)", frames_key="input frames (DATA.NUM_FRAMES)")
         L = lib()
         m = self.m
@@ -417,6 +425,8 @@ class EncoderEngine(GraphReplay):
         C = self.C
         dev = frames.device
         sv = dict(B=B, T=T, N=N, R=R, M=M, Wp=Wp, blocks=[], ckpt=bool(save and self.act_checkpoint))
+        if tokens:
+            sv["tokens"] = True
 
         if isinstance(frames, DecodedClips):     # decoded uint8 clips: GPU-side normalise/rescale/crop/flip + im2col
             a_pe = ops.frames_u8_patchify(frames)
@@ -439,8 +449,10 @@ class EncoderEngine(GraphReplay):
             if self.undivided:
                 x = self._block_fwd_undivided(blk, x, sv, droppath[i], save, ckpt=ckpt)
             else:
-                x = self._block_fwd(blk, x, sv, droppath[i], save, last=last, ckpt=ckpt)
+                x = self._block_fwd(blk, x, sv, droppath[i], save, last=last, ckpt=ckpt, tokens=tokens)
 
+        if tokens:
+            return self._final_norm_tokens(x, sv, frames_per_clip, save)
         if frames_per_clip:         # vit.py:414-416: the mean over the frames, in front of the final norm (only x[:, 0] is read)
             sv["frames_per_clip"] = frames_per_clip
             x = _X(x.p, x.c.view(-1, frames_per_clip, C).mean(1))
@@ -458,6 +470,34 @@ class EncoderEngine(GraphReplay):
                 gs = self.grad_store()
                 lib().call("pvrl_nonfinite_flag_f32", ops._ptr(feat), feat.numel(), ops._ptr(gs.bad), ops._stream())
         return feat
+
+    def _final_norm_tokens(self, x, sv, frames_per_clip, save):
+        """the tail of a tokens forward: norm(x) of every row, written by ONE launch straight into the reference's token order
+        (pvrl_layernorm_fwd_tokens) -> fp32 [B, 1 + P, C]"""
+        m = self.m
+        B, N, T, R, C = sv["B"], sv["N"], sv["T"], sv["R"], self.C
+        P = N * T
+        if frames_per_clip:
+            # `space_only` (vit.py:414-416): the mean over a clip's frames covers every token.  The rows are (b, t, n): as a matrix
+            # [B * T, N * C] the patch rows are groups of T consecutive rows, which is pvrl_group_reduce's grouping -- it reads the
+            # stream's values and accumulates in fp32; the B * T cls rows with torch ops, as in the cls path.  The mean stays fp32.
+            sv["frames_per_clip"] = frames_per_clip
+            B, P = B // frames_per_clip, N
+            full = torch.empty((B * N + B, C), device=x.c.device, dtype=F32)
+            ops.group_reduce(x.p.view(B * frames_per_clip, N * C), B, frames_per_clip, alpha=1.0 / frames_per_clip,
+                             out=full[:B * N].view(B, N * C))
+            full[B * N:] = x.c.view(B, frames_per_clip, C).mean(1)
+            x = _X(full[:B * N], full[B * N:], full)
+        tok, mean, rstd = ops.layernorm_fwd_tokens(x.all(), m.norm.weight.detach(), m.norm.bias.detach(), self.eps, P)
+        self._refreshed = False
+        if save:
+            sv["x_final"] = x
+            sv["norm_stats"] = (mean, rstd)
+            self.saved = sv
+            if SCALED_GRADS:        # (see _forward: an overflowed 16-bit activation raises the optimiser's skip flag)
+                gs = self.grad_store()
+                lib().call("pvrl_nonfinite_flag_f32", ops._ptr(tok), tok.numel(), ops._ptr(gs.bad), ops._stream())
+        return tok.view(B, P + 1, C)
 
     def saved_nbytes(self):
         """bytes the last training forward keeps for its backward: the distinct storages under `self.saved` (storage_nbytes)"""
@@ -535,11 +575,11 @@ class EncoderEngine(GraphReplay):
         self._lin_wgrad(gs, du, s["h_m"], blk.mlp.fc1)
         return ops.gemm_nt(du, self._weight(blk.mlp.fc1.weight).t, L.PVRL_EPI_BF16)
 
-    def _block_fwd(self, blk, x0, sv, dp, save, last=False, ckpt=False, recompute=False):
+    def _block_fwd(self, blk, x0, sv, dp, save, last=False, ckpt=False, recompute=False, tokens=False):
         """`last`: the encoder's last block (with prune_last: the patch rows of x2 / x3 are neither computed nor defined).
         `ckpt` (act_checkpoint, never the last block): the entry saved is x0 and dp alone.  `recompute`: the backward's second pass over
         such a block from that entry -- the full entry again, without the next stage (_mlp_fwd) -> None"""
-        prune = last and self.prune_last
+        prune = last and self.prune_last and not tokens     # (tokens: every row of the last block's output is read)
         keep_u = save and not ckpt
         L = lib()
         B, T, N, R, M = sv["B"], sv["T"], sv["N"], sv["R"], sv["M"]
@@ -712,16 +752,16 @@ class EncoderEngine(GraphReplay):
 
     # ------------------------------------------------------------------ HIP graphs (GraphReplay)
     def _eager_forward(self, frames, training, save):
-        return self._forward(frames, training, None, save)
+        return self._forward(frames, training, None, save, tokens=self._tok)
 
     def _eager_backward(self, dfeat):
-        return self._backward(dfeat)
+        return self._backward(dfeat)          # (what the saved forward returned decides: sv["tokens"], _bwd_begin)
 
     def _graph_key(self, frames, training, save):
         m = self.m
         # parameter / gradient storage is baked into a graph: a re-homed parameter (optimizer flat buffer, .to()) is a new key
         return (tuple(frames.shape), frames.dtype, bool(training), bool(save), bool(self.act_checkpoint), frames.device.index, tuple(m.drop_path_rates),
-                m.blocks[0].attn.qkv.weight.data_ptr(), m.norm.weight.data_ptr(), self.grad_store().flat.data_ptr())
+                m.blocks[0].attn.qkv.weight.data_ptr(), m.norm.weight.data_ptr(), self.grad_store().flat.data_ptr(), bool(self._tok))
 
     def _graph_reset_host_state(self):
         self._wq = []
@@ -739,9 +779,10 @@ class EncoderEngine(GraphReplay):
         return [p for p in ps if p.requires_grad]
 
     # ------------------------------------------------------------------ backward
-    def backward(self, dfeat):
-        """dfeat fp32 [B, C]: gradient of the loss w.r.t. forward()'s output.  Writes every encoder
-        parameter gradient into the GradStore views (p.grad) and returns nothing."""
+    def backward(self, dfeat, tokens=False):
+        """dfeat fp32 [B, C]: gradient of the loss w.r.t. forward()'s output ([B, 1 + N*T, C] after forward(tokens=True): `tokens` must
+        say what the saved forward was).  Writes every encoder parameter gradient into the GradStore views (p.grad) and returns nothing."""
+        assert self.saved is not None and bool(self.saved.get("tokens")) == bool(tokens), "backward(tokens=...) does not match the saved forward"
         if self._gkey is not None:
             return self._graph_backward(dfeat)
         return self._backward(dfeat)
@@ -773,6 +814,8 @@ class EncoderEngine(GraphReplay):
         if SCALED_GRADS:
             dfeat = gs.begin_scaled(dfeat)
         last = len(m.blocks) - 1
+        if sv.get("tokens"):
+            return self._bwd_begin_tokens(dfeat, sv, gs)
         pruned = bool(sv["blocks"][last].get("pruned"))
         split = sv["split"]
         # the residual gradient stream: zero outside the cls rows until the last block's spatial branch.  Split stream + pruned last
@@ -801,6 +844,46 @@ class EncoderEngine(GraphReplay):
         else:
             dy = ops.cast_scale(dx.full, s3)
         return dict(sv=sv, gs=gs, dx=dx, dy=dy, dxp_zero=dxp_zero)
+
+    def _bwd_begin_tokens(self, dtok, sv, gs):
+        """_bwd_begin after forward(tokens=True): dtok fp32 [B, 1 + P, C] (in S-scaled units already).  ONE launch
+        (pvrl_layernorm_bwd_tokens) reads it in the reference's token order and writes the gradient of every row of the stream and,
+        from the same registers, the last block's first operand dy = 16-bit(s3 * dx); norm.weight / norm.bias are sums over all rows."""
+        m = self.m
+        R, M, C = sv["R"], sv["M"], self.C
+        Bp = M - R                      # the stream's cls rows (`space_only`: one per frame)
+        dev = dtok.device
+        split = sv["split"]
+        last = len(m.blocks) - 1
+        s3 = sv["blocks"][last]["dp"]["s3_all"] if sv["blocks"][last]["dp"] else None
+        mean, rstd = sv["norm_stats"]
+        xf = sv["x_final"]
+        (dg, bg), (db, _) = gs.target(m.norm.weight, fused=True), gs.target(m.norm.bias, fused=True)
+        dtok = dtok.contiguous().view(-1, C)
+        dy = torch.empty((M, C), device=dev, dtype=OP16)
+        dx = _X.new(R, Bp, C, dev, split)
+        fpc = sv.get("frames_per_clip", 0)
+        if not fpc:
+            ops.layernorm_bwd(dtok, xf.all(), mean, rstd, m.norm.weight.detach(), dg, db, dx_out=dx.all(), beta_acc=bg, gscale=gs.inv,
+                              nonfinite=gs.bad, defer=self._ln_defer, dxs=dy, dxs_scale=s3, rows_per_clip=sv["N"] * sv["T"])
+            return dict(sv=sv, gs=gs, dx=dx, dy=dy, dxp_zero=False)
+        # `space_only`: the norm saw the mean over a clip's frames of every token (vit.py:414-416) -- its gradient, then 1 / T of it to
+        # each frame's rows: pvrl_group_bcast_bf16 on the [B * T, N * C] view of the (b, t, n) patch rows, once for the stream's gradient
+        # and once with the last block's DropPath factor (one per frame) for dy; the B * T cls rows with torch ops
+        B, N = Bp // fpc, sv["N"]
+        dxm = torch.empty_like(xf.full)
+        ops.layernorm_bwd(dtok, xf.full, mean, rstd, m.norm.weight.detach(), dg, db, dx_out=dxm, beta_acc=bg, gscale=gs.inv,
+                          nonfinite=gs.bad, defer=self._ln_defer, rows_per_clip=N)
+        dpm = dxm[:B * N].view(B, N * C)
+        s3c = s3[R:] if s3 is not None else None
+        ops.group_bcast(dpm, B, fpc, scale=s3c, alpha=1.0 / fpc, out=dy[:R].view(Bp, N * C))
+        if split:
+            ops.group_bcast(dpm, B, fpc, alpha=1.0 / fpc, out=dx.p.view(Bp, N * C))
+        else:       # (the fp32 stream of PVRL_RESID16=0, an A/B switch: no fp32 broadcast kernel is kept for it)
+            dx.p.view(B, fpc, N * C).copy_((dpm / fpc).unsqueeze(1).expand(-1, fpc, -1))
+        dx.c.view(B, fpc, C).copy_((dxm[B * N:] / fpc).unsqueeze(1).expand(-1, fpc, -1))
+        ops.cast_scale(dx.c, s3c, out=dy[R:])
+        return dict(sv=sv, gs=gs, dx=dx, dy=dy, dxp_zero=False)
 
     def _recompute(self, blk, s, sv):
         """a checkpointed block's entry (x0, dp) -> the entry a plain forward would have saved: the block's forward once more (the same

@@ -15,22 +15,22 @@ F32 = torch.float32
 
 
 class EncoderFn(torch.autograd.Function):
-    """frames -> norm(x)[:, 0] through the TimeSformer encoder (engine.EncoderEngine)."""
+    """frames -> norm(x)[:, 0] through the TimeSformer encoder (engine.EncoderEngine); `tokens`: norm(x) of every token, [B, 1 + N*T, C]."""
 
     @staticmethod
-    def forward(ctx, anchor, frames, owner, droppath):
+    def forward(ctx, anchor, frames, owner, droppath, tokens=False):
         eng = owner.engine
         need = bool(ctx.needs_input_grad[0])
         # DropPath lives in the blocks (vit.py:110-117): `model.blocks.eval()` of the linear-probing loop (tools/train_net.py:72-85)
         # switches it off while the wrapper stays in train mode, so the blocks' flag decides, not the wrapper's
-        feat = eng.forward(frames, training=owner.blocks.training, droppath=droppath, save=need)
-        ctx.owner = owner
+        feat = eng.forward(frames, training=owner.blocks.training, droppath=droppath, save=need, tokens=tokens)
+        ctx.owner, ctx.tokens = owner, bool(tokens)
         return feat
 
     @staticmethod
     def backward(ctx, dfeat):
-        ctx.owner.engine.backward(dfeat.contiguous())
-        return None, None, None, None
+        ctx.owner.engine.backward(dfeat.contiguous(), tokens=ctx.tokens)
+        return None, None, None, None, None
 
 
 class StackFn(torch.autograd.Function):

@@ -337,18 +337,46 @@ def layernorm_fwd(x, gamma, beta, eps, out_dtype=OP16, out=None, save_stats=True
     return out, mean, rstd
 
 
+def _as_rows(x):
+    return x if isinstance(x, SplitRows) else SplitRows(None, x)
+
+
+def layernorm_fwd_tokens(x, gamma, beta, eps, rows_per_clip, out=None):
+    """The final norm over every token (pvrl_layernorm_fwd_tokens): `x` fp32 [M, C] or a SplitRows in the engine's row order (B *
+    rows_per_clip patch rows, then the B cls rows) -> (tokens fp32 [M, C] in the reference's order -- clip b's cls row, then its patch
+    rows --, mean, rstd by engine row)"""
+    x = _as_rows(x)
+    M, C = x.shape
+    if out is None:
+        out = torch.empty((M, C), device=x.device, dtype=F32)
+    _chk2d(out, F32)
+    assert out.shape == (M, C)
+    mean = torch.empty(M, device=x.device, dtype=F32)
+    rstd = torch.empty(M, device=x.device, dtype=F32)
+    xr = x.c_rows()
+    lib().call("pvrl_layernorm_fwd_tokens", ctypes.addressof(xr), _ptr(gamma), _ptr(beta), float(eps), _ptr(out), _ld(out), _ptr(mean),
+               _ptr(rstd), M, C, int(rows_per_clip), _stream())
+    return out, mean, rstd
+
+
 def layernorm_bwd(dy, x, mean, rstd, gamma, dgamma, dbeta, dx_in=None, dx_out=None, beta_acc=0.0, dxs=None, dxs_scale=None,
-                  dxsum=None, dxsum_beta=None, gscale=None, nonfinite=None, defer=None):
+                  dxsum=None, dxsum_beta=None, gscale=None, nonfinite=None, defer=None, rows_per_clip=None):
     """`x`: fp32 [M, C] (pvrl_layernorm_bwd), or a SplitRows (pvrl_layernorm_bwd_split): dx_in (optional; a None part reads as zeros)
     and dx_out are then SplitRows with the same split.
+    `rows_per_clip`: dy is the fp32 token gradient [M, C] in the reference's token order (pvrl_layernorm_bwd_tokens); x, dx_in and
+    dx_out -- tensors or SplitRows -- keep the engine's rows.
     `dxs` (optional bf16 [rows <= M, C]) additionally receives bf16(dxs_scale[m] * dx_out[m]); `dxsum` (optional fp32
     [C]) the unscaled column sums of those rows of dx_out (dxsum = dxsum_beta * dxsum + sums).
     `defer` (a list): the per-workgroup partial sums of dgamma / dbeta / dxsum stay in a private workspace and an entry is appended
     for `layernorm_bwd_reduce_batched`, which reduces many LayerNorms' partials in one launch."""
     L = lib()
+    if rows_per_clip is not None:
+        assert dy.dtype == F32 and dx_out is not None
+        x, dx_out, dx_in = _as_rows(x), _as_rows(dx_out), (None if dx_in is None else _as_rows(dx_in))
     split = isinstance(x, SplitRows)
     _chk2d(dy)
     M, C = x.shape
+    assert rows_per_clip is None or dy.shape == (M, C)
     if split:
         assert isinstance(dx_out, SplitRows) and dx_out.n_lo == x.n_lo and (dx_in is None or (isinstance(dx_in, SplitRows) and dx_in.n_lo == x.n_lo))
         xr, dor = x.c_rows(), dx_out.c_rows()
@@ -371,7 +399,10 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, dgamma, dbeta, dx_in=None, dx_out=No
     tail = (float(beta_acc), None if deferred else _ptr(dgamma), None if deferred else _ptr(dbeta), _ptr(ws), ws.numel(), M, C,
             *_ptr_ld(dxs), _ptr(dxs_scale), dxs.shape[0] if dxs is not None else 0, _ptr(tgt),
             None if deferred else _ptr(gscale), None if deferred else _ptr(nonfinite), _stream())
-    if split:
+    if rows_per_clip is not None:
+        L.call("pvrl_layernorm_bwd_tokens", *head[:2], ctypes.addressof(xr), _ptr(mean), _ptr(rstd), _ptr(gamma),
+               ctypes.addressof(dir_) if dir_ is not None else None, ctypes.addressof(dor), *tail[:7], int(rows_per_clip), *tail[7:])
+    elif split:
         L.call("pvrl_layernorm_bwd_split", *head, ctypes.addressof(xr), _ptr(mean), _ptr(rstd), _ptr(gamma),
                ctypes.addressof(dir_) if dir_ is not None else None, ctypes.addressof(dor), *tail)
     else:

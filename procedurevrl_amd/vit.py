@@ -238,15 +238,15 @@ class VisionTransformer(nn.Module):
 
     # ----------------------------------------------------------------------------- forward
     def forward_features(self, x, cls=True, droppath=None):
-        """x fp32 [B, 3, T, H, W] -> [B, embed_dim] (vit.py:365-423 with cls=True)."""
+        """x fp32 [B, 3, T, H, W] (or transform.DecodedClips) -> [B, embed_dim] (vit.py:365-423 with cls=True); cls=False: the normalised
+        output of every token, fp32 [B, 1 + N*T, embed_dim] -- token 0 is cls, token 1 + n*T + t patch n of frame t ([B, 1 + N, embed_dim]
+        for `space_only`, whose frames are averaged in front of the norm, vit.py:414-418)."""
         if not x.is_cuda:
             raise RuntimeError("procedurevrl_amd runs on the HIP path only: move the model and inputs to the GPU "
                                "(the CPU restatement lives in oracle/ and is test infrastructure)")
-        if not cls:
-            raise NotImplementedError("forward_features(cls=False) has no caller on the hot path")
         if self.training and torch.is_grad_enabled():
             self.grad_store()
-        return EncoderFn.apply(self.cls_token, x.float(), self, droppath)
+        return EncoderFn.apply(self.cls_token, x.float(), self, droppath, not cls)
 
     def get_pseudo_labels(self, device, text):
         """vit.py:425-433"""
