@@ -81,6 +81,8 @@ def storage_nbytes(obj, seen=None):
 
 
 class EncoderEngine(GraphReplay):
+    DWE_LIMIT = 32768.0     # fp16 flavour: the largest |S-scaled dW_e| its 16-bit copies are allowed to hold, 2 x below 65,504 (_temporal_chain_all)
+
     def __init__(self, model):
         """`model` is a procedurevrl_amd.vit.VisionTransformer (same parameter names as the reference)."""
         self.m = model
@@ -96,6 +98,7 @@ class EncoderEngine(GraphReplay):
         self._grads = None
         self.saved = None
         self.grad_hook = None
+        self._dwe_rescale = False
         # ONE STREAM since round 5.  Until round 4 the weight-gradient GEMMs ran on a side stream next to the dgrad chain and the
         # fused temporal maps W_e were built on it at the start of the forward.  Measured (profiles/r5_hw_queues.txt, two passes):
         # single stream 636.5 clips/s, W_e prefetch only 632.3, both 622.7 -- and only the single-stream step is independent of how
@@ -247,24 +250,47 @@ class EncoderEngine(GraphReplay):
         rs = gs.inv_row if gs.inv is not None else None
         dev = chain[0][1].device
         C = self.C
+        rss = [rs] * len(chain)
+        if rs is not None and self._dwe_rescale:
+            # dW_e is the one S-scaled SUM OVER ALL PATCH ROWS that is rounded to 16 bits.  Under an all-token gradient (forward(tokens=True):
+            # up to 256 in S units on EVERY row, not on one row per clip) it grows with the row count and passes fp16's 65,504 (mean-pooled
+            # tokens, 32 clips of 8 x 224^2: 2.4e5).  There its copies get a power of two of their own, 2^-e with the
+            # smallest e >= 0 that brings max|dW_e| under DWE_LIMIT, chosen on the device; 2^e goes into the row scale of the two GEMMs
+            # (db_e is used in fp32).  Exact, and e = 0 -- nothing changes, not a bit -- below the limit.  The cls path (measured 100 x
+            # below 65,504 at the same row count) keeps its launches as they are.
+            amax = torch.nan_to_num(torch.stack(torch._foreach_norm([dwe for _, dwe, _ in chain], float("inf"))), nan=1.0, posinf=3e38)
+            e = torch.ceil(torch.log2(amax.clamp_min(1e-30) / self.DWE_LIMIT)).clamp(0.0, 100.0)
+            for (_, dwe, _), f in zip(chain, torch.exp2(-e).unbind(0)):
+                dwe.mul_(f)
+            rss = list((torch.exp2(e).unsqueeze(1) * rs.unsqueeze(0)).unbind(0))
         items = []
         for blk, dwe, dbe in chain:
             items.append((dwe, torch.empty((C, C), device=dev, dtype=OP16), torch.empty((C, C), device=dev, dtype=OP16)))
         ops.cast_weights_multi(items)
         groups = {0.0: [], 1.0: []}
-        for (blk, dwe, dbe), (_, dwe_b, dwe_t) in zip(chain, items):
+        fresh = {}      # id(blk) -> (temporal_fc.weight gradient that is already there, the new one): see below
+        for (blk, dwe, dbe), (_, dwe_b, dwe_t), rsi in zip(chain, items, rss):
             wf, wp = blk.temporal_fc.weight, blk.temporal_attn.proj.weight
             ef, ep = self._weight(wf), self._weight(wp)
             for lin_w, A, W in ((wf, dwe_b, ep.w), (wp, ef.t, dwe_t)):       # [out,mid] = dW_e.W_p^T ; [mid,in] = W_f^T.dW_e
                 # (gemm_nt_batched / rank1_add / gemv_rows take no `nonfinite` argument: checks=False keeps these parameters in the optimiser's scan)
                 g, beta = gs.target(lin_w, fused=True, checks=False)
-                groups[beta].append(dict(A=A, W=W, rowscale=rs, out0=g, aux=g if beta else None))
+                if beta and lin_w is wf:
+                    # dW_fc is written in two steps (this GEMM, then the rank-1 term db_e b_proj^T) that may cancel: added one after the
+                    # other to a gradient that is already there, each rounds at ITS OWN size, not the sum's.  An accumulating step
+                    # (eager launches, never captured) forms the new gradient first and adds it once: one rounding of the sum.
+                    fresh[id(blk)] = (g, torch.empty_like(g))
+                    g, beta = fresh[id(blk)][1], 0.0
+                groups[beta].append(dict(A=A, W=W, rowscale=rsi, out0=g, aux=g if beta else None))
         if groups[0.0]:
             ops.gemm_nt_batched(groups[0.0], L.PVRL_EPI_F32)
         if groups[1.0]:
             ops.gemm_nt_batched(groups[1.0], L.PVRL_EPI_RESID_F32)
-        ops.rank1_add_batched([gs.target(blk.temporal_fc.weight, fused=True, checks=False)[0] for blk, _, _ in chain], [dbe for _, _, dbe in chain],
-                              [blk.temporal_attn.proj.bias.detach() for blk, _, _ in chain], gscale=gs.inv)
+        ops.rank1_add_batched([fresh[id(blk)][1] if id(blk) in fresh else gs.target(blk.temporal_fc.weight, fused=True, checks=False)[0]
+                               for blk, _, _ in chain],
+                              [dbe for _, _, dbe in chain], [blk.temporal_attn.proj.bias.detach() for blk, _, _ in chain], gscale=gs.inv)
+        for g, new in fresh.values():
+            g.add_(new)
         tb = [gs.target(blk.temporal_attn.proj.bias, fused=True, checks=False) for blk, _, _ in chain]
         ops.gemv_rows_batched([self._weight(blk.temporal_fc.weight).t for blk, _, _ in chain], [dbe for _, _, dbe in chain],
                               [t for t, _ in tb], [b for _, b in tb], gscale=gs.inv)
@@ -811,6 +837,7 @@ class EncoderEngine(GraphReplay):
         R, M = sv["R"], sv["M"]
         self._chain = []
         self._ln_defer = []
+        self._dwe_rescale = bool(sv.get("tokens"))        # (_temporal_chain_all)
         if SCALED_GRADS:
             dfeat = gs.begin_scaled(dfeat)
         last = len(m.blocks) - 1

@@ -124,7 +124,11 @@ class GradStore:
     # DEVICE from that gradient's magnitude (no host sync, capturable in a HIP graph), runs its whole backward in S-scaled
     # units -- exact in fp32, and the 16-bit operands sit mid-range -- and multiplies every parameter gradient it produced
     # by 1/S before anyone outside the engine sees it.  Nothing outside the engine ever holds a scaled value.
-    SCALE_TARGET = 256.0          # S * max|incoming gradient|; the largest internal operand stays ~100x below fp16's 65504
+    # S * max|incoming gradient|.  The only internal 16-bit operand that can outgrow it is an S-scaled SUM OVER ROWS: dW_e of the encoder's
+    # fused temporal map (engine._temporal_chain_all).  Measured headroom below fp16's 65,504 (tests/test_grad_scale_gpu.py):
+    # cls path ~100 x; all-token gradients at 288 rows 57 x (N(0,1)) / 8 x (mean-pooled), at 50,176 rows 4.8 x / 0.27 x -- so under an
+    # all-token gradient the dW_e copies carry a power of two of their own and enter the cast 2.2 x below.
+    SCALE_TARGET = 256.0
 
     def begin_scaled(self, g):
         """g: the fp32 gradient entering the engine -> g * S; registers S for target() / unscale()"""

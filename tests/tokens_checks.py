@@ -91,16 +91,17 @@ def undivided_block(sd, pre, x, num_heads):
     return torch.cat((x[:, :1], rorc.RX(x[:, 1:])), 1)
 
 
-def oracle_tokens(f, sd, x, rounded=None):
+def oracle_tokens(f, sd, x, rounded=None, grad=False):
     """norm(x) of every token [B, 1 + N*T, C] ([B, 1 + N, C] for space_only) on the CPU: rounded_oracle.forward_features' embedding prologue
     and blocks, then the final norm over ALL rows.  `rounded` None: plain fp32 (the reference's arithmetic); a 16-bit dtype: the HIP
-    datapath's rounding points, the 16-bit patch rows of the split residual stream included."""
+    datapath's rounding points, the 16-bit patch rows of the split residual stream included.  `grad`: keep the autograd graph (sd holds
+    leaves that require a gradient: tests/grad_scale_checks.py back-propagates a chosen dtok through it)."""
     scheme, heads, depth = f["type"], f["heads"], f["depth"]
     dp = droppath_oracle(f)
     prev_resid = rorc.RESID
     rorc.RESID = "both" if rounded is not None else None
     try:
-        with rorc.operand(rounded), torch.no_grad():
+        with rorc.operand(rounded), torch.set_grad_enabled(bool(grad)):
             B, _, T, _, _ = x.shape
             xx = rearrange(rorc.R(x), "b c t h w -> (b t) c h w")
             xx = rorc.RB(F.conv2d(xx, rorc.RW(sd["patch_embed.proj.weight"]), sd["patch_embed.proj.bias"], stride=16))
