@@ -16,9 +16,13 @@ DEV = "cuda:0"
 # bf16: features / logits 4.9-6.2e-3, losses <= 1.1e-3, gradients <= 1.8e-2 (rel_pos_h 4.2e-2: signed sums, cancellation);
 # f16 (the flavour held to north_star's 1e-3): features / logits 6.1-7.8e-4, losses <= 1.3e-4, gradients <= 1.8e-3.
 F16 = OPERAND != "bf16"
-TOL_FEAT = 1e-3 if F16 else 1e-2
+def flavour_tols(f16):
+    """-> (TOL_FEAT, GSC) of a flavour; GSC: scale of every gradient tolerance below (f16: 8x smaller rounding, ~4x smaller errors)"""
+    return (1e-3, 1.0 / 3.0) if f16 else (1e-2, 1.0)
+
+
+TOL_FEAT, GSC = flavour_tols(F16)
 TOL_LOSS = 1e-3 if F16 else 2.5e-3
-GSC = 1.0 / 3.0 if F16 else 1.0          # scale of every gradient tolerance below (f16: 8x smaller rounding, ~4x smaller errors)
 
 
 def bf(x):
@@ -287,21 +291,28 @@ def check_mvit_encoder_small_golden():
     out = [("mvit state_dict keys == reference", float(sorted(vt.video_encoder.state_dict().keys()) != g["keys"]), 0.0)]
     model.train()
     feat = vt.forward_features(g["x"].to(DEV))
-    out.append(("mvit small features vs reference", rel(feat, g["feat"]), TOL_FEAT))
     (feat * g["gout"].to(DEV)).sum().backward()
     params = dict(vt.video_encoder.named_parameters())
+    return out + small_golden_findings(g, feat, {n: params[n].grad for n in g["grads"]})
+
+
+def small_golden_findings(g, feat, grads, f16=F16):
+    """the flat bounds of check_mvit_encoder_small_golden on features and gradients computed from the fixture's x and gout by any path (the
+    HIP encoder there; a CPU model in tests/test_mvit_rounding_host.py) -> [(label, value, bound)]"""
+    tol_feat, gsc = flavour_tols(f16)
+    out = [("mvit small features vs reference", rel(feat, g["feat"]), tol_feat)]
     for n, ref in g["grads"].items():
-        got = params[n].grad
+        got = grads[n]
         got = got[:64] if got.dim() == 2 else got
         err = float((got.detach().float().cpu() - ref).norm())
         if n.endswith("norm_k.bias"):
             # a common shift of every key is softmax-invariant: the true gradient is 0 (the reference holds 4e-6 of fp32
             # noise); the bf16 path's residue is bounded against the sibling gain gradient instead
-            tol = GSC * (5e-2 * float(g["grads"].get(n.replace("norm_k.bias", "norm_q.weight"), ref).norm()) + 1e-3)
+            tol = gsc * (5e-2 * float(g["grads"].get(n.replace("norm_k.bias", "norm_q.weight"), ref).norm()) + 1e-3)
         elif "rel_pos" in n:
-            tol = GSC * (6e-2 * float(ref.norm()) + 1e-4 * ref.numel() ** 0.5)   # signed sums over all queries: cancellation
+            tol = gsc * (6e-2 * float(ref.norm()) + 1e-4 * ref.numel() ** 0.5)   # signed sums over all queries: cancellation
         else:
-            tol = GSC * (3e-2 * float(ref.norm()) + 1e-4 * ref.numel() ** 0.5)
+            tol = gsc * (3e-2 * float(ref.norm()) + 1e-4 * ref.numel() ** 0.5)
         out.append((f"mvit small d {n} (abs err / allowed)", err / tol, 1.0))
     return out
 

@@ -66,9 +66,10 @@ import pool_attn_checks as pc
 from pool_attn_checks import Finding, Guarded, guarded_input, rowerr, agg, ROW_FACTOR, MIN_ROWS, report, BF  # noqa: F401 (re-exported)
 from attn_checks import judge_tensor
 from oracle import mvit_oracle as mo
+from oracle import mvit_rounded_oracle as mro
 
 D = 96
-EPS = 1e-6
+EPS = mro.EPS
 AGG_FWD, AGG_BWD = 6e-3, 1.5e-2          # mvit_checks.check_mvit_pool
 REL_Y_FACTOR = pc.REL_Y_FACTOR
 WS_TAIL, WS_FILL = pc.WS_TAIL, pc.WS_FILL
@@ -265,11 +266,6 @@ def pool_reference(p, c):
                 dbeta=p["dbeta0"].double() + gb)
 
 
-def _ln_stats(v):
-    mu = v.mean(-1, keepdim=True)
-    return mu, torch.rsqrt((v - mu).pow(2).mean(-1, keepdim=True) + EPS)
-
-
 def pool_model(p, c, operand, variant=False, defect=None):
     """the kernels' rounding model (module docstring) -> y, c, dc, dX (16-bit-valued), dw, dgamma, dbeta (fp32, start + gradient).
     defect: one of the structural defects tests/test_mvit_pool_harness_host.py plants (`POOL_DEFECTS`)."""
@@ -296,13 +292,10 @@ def pool_model(p, c, operand, variant=False, defect=None):
         conv32 = torch.where(last[None, :, None], alt, conv32)
     elif defect == "cls_through_conv":              # the cls token is multiplied by the centre tap
         conv32 = torch.cat((conv32[:, :-1], conv32[:, -1:] * wg[:, 13]), 1)
-    cr = _rnd(conv32.detach(), operand)
-    mu_f, rs_f = _ln_stats(cr if variant else conv32.detach())
-    y = _rnd((conv32.detach() - mu_f) * rs_f * gm + bt, operand)
-    mu, rs = _ln_stats(cr)
-    xh = (cr - mu) * rs
-    gg = dy * gm
-    dc = _rnd(rs * (gg - gg.mean(-1, keepdim=True) - xh * (gg * xh).mean(-1, keepdim=True)), operand)
+    # the rounding points themselves: oracle/mvit_rounded_oracle.py (one restatement of the kernels for the per-token and the end-to-end rule)
+    rnd = lambda t: _rnd(t, operand)
+    cr, y = mro.pool_ln_fwd(conv32.detach(), gm, bt, rnd, variant)
+    dc, xh = mro.pool_ln_bwd(cr, gm, dy, rnd)
     dcg = dc.clone()
     dc_w = dc.clone()
     if defect == "dgrad_drops_last_output_row" and c.thw[1] % 2 == 1:

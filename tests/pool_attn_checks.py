@@ -37,6 +37,7 @@ import torch.nn.functional as F
 import attn_checks as ac
 from attn_checks import Finding, Guarded, guarded_input, rowerr, agg, ROW_FACTOR, MIN_ROWS, report  # noqa: F401 (re-exported)
 from oracle import mvit_oracle as mo
+from oracle import mvit_rounded_oracle as mro
 
 BF = ac.BF
 D = 96
@@ -165,22 +166,12 @@ def n_draws(c):
 # ---------------------------------------------------------------------------------------------------------------------
 # inputs
 # ---------------------------------------------------------------------------------------------------------------------
-def key_map(k_thw):
-    """E [Lk, J] (fp32 0/1): the columns mvit_checks._attn_ref indexes"""
-    kt, kh, kw = k_thw
-    Lk = kt * kh * kw
-    j = torch.arange(Lk)
-    E = torch.zeros(Lk, kt + kh + kw)
-    E[j, (j // kw) % kh] = 1
-    E[j, kh + j % kw] = 1
-    E[j, kh + kw + j // (kw * kh)] = 1
-    return E
+key_map = mro.key_map          # E [Lk, J] (fp32 0/1): the columns mvit_checks._attn_ref indexes
 
 
 def pack(x, dt):
     """fp32 -> the hi, lo pair of the operand type (as fp32 tensors)"""
-    hi = _rnd(x, dt)
-    return hi, _rnd(x - hi, dt)
+    return mro.pack(x, lambda t: _rnd(t, dt))
 
 
 def make_problem(c, regime, operand=None, draw=0):
@@ -230,11 +221,7 @@ def from_tok(t, B, H):
 # ---------------------------------------------------------------------------------------------------------------------
 def rel_terms(Qp, Rh, Rw, Rt, p, q_thw, flip=False):
     """Qp [n, Lq, 96] -> rel [n, Lq, J]; flip: the channels are summed in reverse order (a second implementation for the host test)"""
-    if flip:
-        Qp, Rh, Rw, Rt = (t.flip(-1) for t in (Qp, Rh, Rw, Rt))
-    rq = Qp.reshape(Qp.shape[0], *q_thw, D)
-    return torch.cat((torch.einsum("bthwc,hkc->bthwk", rq, Rh[p["ih"]]), torch.einsum("bthwc,wkc->bthwk", rq, Rw[p["iw"]]),
-                      torch.einsum("bthwc,tkc->bthwk", rq, Rt[p["it"]])), -1).reshape(Qp.shape[0], Qp.shape[1], -1)
+    return mro.rel_terms(Qp, Rh, Rw, Rt, (p["ih"], p["iw"], p["it"]), q_thw, flip)
 
 
 def _paired(x, dt):
@@ -324,33 +311,15 @@ def pool_model(p, c, operand, hi=None, lo=None, variant=False, E_kernel=None, cl
     hi = p["hi"] if hi is None else hi
     lo = p["lo"] if lo is None else lo
     out = []
+    rnd = lambda t: _rnd(t, operand)
     for sl in _slices(p["q"].shape[0], Lq + 1, Lk + 1):
         ql, kl, vl, dl = (p[n][sl] for n in ("q", "k", "v", "do"))
-        t = ql @ kl.transpose(1, 2)
-        bias = hi[sl] @ E.t() + lo[sl] @ E.t()
-        t[:, :Lq, :Lk] += bias
-        if cls_bias:
-            t[:, Lq, :Lk] += bias[:, Lq - 1]
-        s = t * SCALE
-        m = s.amax(-1, keepdim=True)
-        pt = torch.exp(s - m)
-        l = pt.sum(-1, keepdim=True)
-        lse = m + torch.log(l)
-        res = ql.clone()
-        dres = dl.clone()
-        if not cls_resid:
-            res[:, Lq] = 0
-            dres[:, Lq] = 0
-        oa = _rnd(pt / l, operand) @ vl if variant else (_rnd(pt, operand) @ vl) / l
-        o = _rnd(oa + res, operand)
-        P = torch.exp(s - lse)
-        delta = (dl * (oa if variant else o - res)).sum(-1, keepdim=True)
-        ds = _rnd(P * (dl @ vl.transpose(1, 2) - delta), operand)
-        r = dict(o=o, lse=lse[..., 0], delta=delta, dq=_rnd(SCALE * (ds @ kl) + dres, operand),
-                 dk=_rnd(SCALE * (ds.transpose(1, 2) @ ql), operand), dv=_rnd(_rnd(P, operand).transpose(1, 2) @ dl, operand),
-                 drel=ds[:, :Lq, :Lk] @ E)
+        # the arithmetic itself: oracle/mvit_rounded_oracle.py (one restatement of the kernel for the per-row and the end-to-end rule)
+        f = mro.pattn_fwd(ql, kl, vl, hi[sl], lo[sl], E, SCALE, rnd, variant, cls_bias, cls_resid)
+        b = mro.pattn_bwd(ql, kl, vl, dl, f, E, SCALE, rnd, variant, cls_resid)
+        r = dict(o=f["o"], lse=f["lse"][..., 0], delta=b["delta"], dq=b["dq"], dk=b["dk"], dv=b["dv"], drel=b["drel"])
         if keep_ds:
-            r["ds"] = ds
+            r["ds"] = b["ds"]
         out.append(r)
     return _cat(out)
 
