@@ -333,6 +333,27 @@ int pvrl_adam_step(float* p, const float* g, float* m, float* v, int64_t n, doub
                    double eps, double weight_decay, int64_t step, double gscale, int decoupled, const float* skip, void* stream);
 int pvrl_sgd_step(float* p, const float* g, float* buf, int64_t n, double lr, double momentum, double dampening,
                   double weight_decay, int nesterov, int first_step, double gscale, const float* skip, void* stream);
+/* Global-norm gradient clipping (torch.nn.utils.clip_grad_norm_; SOLVER.CLIP_GRAD_L2NORM) fused into the step: no host-visible scalar, no
+ * pass that rescales the gradients, no atomics -- the same calls over the same bytes give the same bits.
+ * pvrl_sumsq_f32: one streaming pass over g[0, n) (16-byte aligned) that writes pvrl_sumsq_slots(n) fp64 partial sums of squares -- one
+ *   per workgroup; squares and sums in fp64 -- to ws[slot ...] (ws: 8-byte aligned doubles, ws_slots of them: a call that would write
+ *   behind them is refused), and raises *flag when an element is inf / nan (the bit test of pvrl_nonfinite_flag_f32, whose launch it
+ *   replaces).  Several runs are laid into one workspace at consecutive slot offsets.  n <= 0: nothing is written.
+ * pvrl_sumsq_slots: pure host function (0 for n <= 0).
+ * pvrl_clip_coef: one workgroup adds ws[0, nslots) in fp64 in a fixed order and writes out[0] = norm = fp32(fp32(gscale) * sqrt(sum)) (the
+ *   norm of what the update applies), out[1] = coef = min(1, max_norm / (norm + 1e-6f)) in fp32, and raises *flag when the norm is not
+ *   finite.  max_norm <= 0 (or nan) is refused.  nslots = 0: norm 0, coef 1.
+ * pvrl_adam_step_clip / pvrl_sgd_step_clip: pvrl_adam_step / pvrl_sgd_step with `clip` (device pointer or null): the update uses
+ *   (g * gscale) * *clip.  Null is the arithmetic of the entry points above bit for bit (they pass null). */
+int64_t pvrl_sumsq_slots(int64_t n);
+int pvrl_sumsq_f32(const float* g, int64_t n, void* ws, int64_t slot, int64_t ws_slots, float* flag, void* stream);
+int pvrl_clip_coef(const void* ws, int64_t nslots, double gscale, double max_norm, float* out, float* flag, void* stream);
+int pvrl_adam_step_clip(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
+                        double eps, double weight_decay, int64_t step, double gscale, int decoupled, const float* skip,
+                        const float* clip, void* stream);
+int pvrl_sgd_step_clip(float* p, const float* g, float* buf, int64_t n, double lr, double momentum, double dampening,
+                       double weight_decay, int nesterov, int first_step, double gscale, const float* skip, const float* clip,
+                       void* stream);
 /* *flag = 1 when any of x[0, n) is inf / nan; never cleared here (zero it, then chain the buffers to check).  x 16-byte aligned. */
 int pvrl_nonfinite_flag_f32(const float* x, int64_t n, float* flag, void* stream);
 /* The fp16-operand flavour's per-backward gradient scale (procedurevrl_amd/engine.py GradStore.begin_scaled) in one launch: S = the power of

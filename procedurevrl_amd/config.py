@@ -199,7 +199,9 @@ _DEFAULTS = {
     "SOLVER": {"BASE_LR": 0.1, "LR_POLICY": "cosine", "COSINE_END_LR": 0.0, "GAMMA": 0.1, "STEP_SIZE": 1, "STEPS": [],
                "LRS": [], "MAX_EPOCH": 300, "MOMENTUM": 0.9, "DAMPENING": 0.0, "NESTEROV": True, "WEIGHT_DECAY": 1e-4,
                "WARMUP_FACTOR": 0.1, "WARMUP_EPOCHS": 0.0, "WARMUP_START_LR": 0.01, "OPTIMIZING_METHOD": "sgd",
-               "BASE_LR_SCALE_NUM_SHARDS": False},
+               "BASE_LR_SCALE_NUM_SHARDS": False,
+               # global-norm gradient clipping inside the fused optimiser step (upstream SlowFast's key); 0.0 = off
+               "CLIP_GRAD_L2NORM": 0.0},
     "NUM_GPUS": 1, "NUM_SHARDS": 1, "SHARD_ID": 0, "OUTPUT_DIR": "./tmp", "RNG_SEED": 1, "LOG_PERIOD": 10,
     "LOG_MODEL_INFO": False, "DIST_BACKEND": "nccl", "GLOBAL_BATCH_SIZE": 64,
     "BENCHMARK": {"NUM_EPOCHS": 5, "LOG_PERIOD": 100, "SHUFFLE": True},

@@ -18,8 +18,17 @@ namespace {
 // apart, the division is kept; Tensor.lerp_ switches formula at weight 0.5, mirrored below (beta1 < 0.5 takes the other one).
 struct AdamConst { float decay, wd, w1, b2, w2, step_size, bc2_sqrt, eps, gscale; int decoupled; };
 
-__device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, const AdamConst& c) {
+// `skip` (device flag, may be null): non-zero = this step must not be applied (a non-finite loss or gradient was seen on the
+// device -- tools/train_net.py:174 `misc.check_nan_losses` raises BEFORE optimizer.step(); the host here reads its metrics only every
+// LOG_PERIOD iterations, so the bad step is dropped on the device and reported at the next log point).
+// `clip` (device scalar; null selects CLIP = false): the clip coefficient of this step (clip_coef_kernel below), read once per thread
+// in front of the loop: gg = (g * gscale) * *clip.  ONE kernel per method, instantiated with and without the operand: the instantiation
+// without it is compiled on its own and is the arithmetic of the entry points that take no `clip`, bit for bit (sharing one function
+// body between the two changed the compiler's choice among the legal fma contractions in the scalar tail).
+template <bool CLIP>
+__device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, const AdamConst& c, float cl) {
   float gg = g * c.gscale;
+  if (CLIP) gg *= cl;
   if (c.decoupled) p *= c.decay; else gg += c.wd * p;
   m = c.w1 < 0.5f ? m + c.w1 * (gg - m) : gg - (gg - m) * (1.f - c.w1);
   v = c.b2 * v + c.w2 * gg * gg;
@@ -27,13 +36,12 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
   p -= c.step_size * (m / denom);
 }
 
-// `skip` (device flag, may be null): non-zero = this step must not be applied (a non-finite loss or gradient was seen on the
-// device -- tools/train_net.py:174 `misc.check_nan_losses` raises BEFORE optimizer.step(); the host here reads its metrics only every
-// LOG_PERIOD iterations, so the bad step is dropped on the device and reported at the next log point).
+template <bool CLIP>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, long n, AdamConst c,
-                                                   const float* __restrict__ skip) {
+                                                   const float* __restrict__ skip, const float* __restrict__ clip) {
   if (skip && *skip != 0.f) return;
+  const float cl = CLIP ? *clip : 1.f;
   for (long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (long)gridDim.x * 1024) {
     if (i + 4 <= n) {
       f32x4 pv = *reinterpret_cast<f32x4*>(p + i);
@@ -43,27 +51,31 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float pe = pv[e], me = mv[e], ve = vv[e];
-        adam_one(pe, gv[e], me, ve, c);
+        adam_one<CLIP>(pe, gv[e], me, ve, c, cl);
         pv[e] = pe; mv[e] = me; vv[e] = ve;
       }
       *reinterpret_cast<f32x4*>(p + i) = pv;
       *reinterpret_cast<f32x4*>(m + i) = mv;
       *reinterpret_cast<f32x4*>(v + i) = vv;
     } else {
-      for (long j = i; j < n; ++j) adam_one(p[j], g[j], m[j], v[j], c);
+      for (long j = i; j < n; ++j) adam_one<CLIP>(p[j], g[j], m[j], v[j], c, cl);
     }
   }
 }
 
+template <bool CLIP>
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                   float* __restrict__ buf, long n, float lr, float momentum,
                                                   float one_minus_damp, float wd, int nesterov, int first, float gscale,
-                                                  const float* __restrict__ skip) {
+                                                  const float* __restrict__ skip, const float* __restrict__ clip) {
   if (skip && *skip != 0.f) return;
+  const float cl = CLIP ? *clip : 1.f;
   // torch.optim.SGD: g += wd * p;  buf = g (first update) | momentum * buf + (1 - dampening) * g;
   //                  g = g + momentum * buf (nesterov) | buf;  p -= lr * g
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    float gg = g[i] * gscale + wd * p[i];
+    float gg;
+    if (CLIP) gg = g[i] * gscale * cl + wd * p[i];
+    else gg = g[i] * gscale + wd * p[i];
     if (momentum != 0.f) {
       const float b = first ? gg : momentum * buf[i] + one_minus_damp * gg;
       buf[i] = b;
@@ -86,6 +98,74 @@ __global__ __launch_bounds__(256) void nonfinite_kernel(const float* __restrict_
     }
   }
   if (__any(bad) && (threadIdx.x & 63) == 0) *flag = 1.f;
+}
+
+// Global-norm gradient clipping (torch.nn.utils.clip_grad_norm_, SOLVER.CLIP_GRAD_L2NORM) without a host-visible scalar and without a
+// pass that rescales the gradients: sumsq_kernel streams a contiguous run of the flat gradient buffer once and leaves one fp64 partial
+// sum of squares per workgroup, clip_coef_kernel adds the partials of every run and writes {norm, coefficient} to a two-float device
+// slot, and the update kernels above multiply by the coefficient (`clip`).  Everything is a plain store to a slot only its writer
+// touches: no atomics, no fences, and the same launches over the same bytes give the same bits.
+// The squares and every sum are fp64: the product of two floats is exact in a double (no overflow at |g| = 2^70, no denormal squares
+// at 2^-70), and the fp64 FMAs run under the HBM stream.  The pass is also the non-finite scan of its range (nonfinite_kernel's bit
+// test), so a step that clips needs no pvrl_nonfinite_flag_f32 launch.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ x, long n, double* __restrict__ slots,
+                                                    float* __restrict__ flag) {
+  __shared__ double red[4];
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  bool bad = false;
+  for (long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (long)gridDim.x * 1024) {
+    if (i + 4 <= n) {
+      const f32x4 w = *reinterpret_cast<const f32x4*>(x + i);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        bad |= (__float_as_uint(w[e]) & 0x7f800000u) == 0x7f800000u;
+        const double d = (double)w[e];
+        acc[e] = fma(d, d, acc[e]);
+      }
+    } else {
+      for (long j = i; j < n; ++j) {
+        bad |= (__float_as_uint(x[j]) & 0x7f800000u) == 0x7f800000u;
+        const double d = (double)x[j];
+        acc[0] = fma(d, d, acc[0]);
+      }
+    }
+  }
+  const double a = wave_sum_f64((acc[0] + acc[1]) + (acc[2] + acc[3]));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) slots[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  if (__any(bad) && (threadIdx.x & 63) == 0) *flag = 1.f;
+}
+
+// One workgroup.  Thread t adds slots t, t + 256, ... in increasing index, then a fixed tree over the 256 threads: the order depends on
+// the slot indices alone (a single lane adding a few thousand slots one after the other would be a chain of dependent fp64 adds as long
+// as the streaming pass itself).  norm = fp32(fp32(gscale) * sqrt(sum)), the product taken in fp64 and rounded once;
+// coef = min(1, max_norm / (norm + 1e-6f)) in fp32 (torch's clip_grad_norm_: `max_norm / (total_norm + 1e-6)`, clamped at 1; a NaN
+// norm gives a NaN coefficient there and here).  A norm that is not finite raises `flag`: this kernel sits in front of every update.
+__global__ __launch_bounds__(256) void clip_coef_kernel(const double* __restrict__ slots, long nslots, float gscale, float max_norm,
+                                                        float* __restrict__ out, float* __restrict__ flag) {
+  __shared__ double red[256];
+  double a = 0.0;
+  for (long i = threadIdx.x; i < nslots; i += 256) a += slots[i];
+  red[threadIdx.x] = a;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float norm = (float)((double)gscale * sqrt(red[0]));
+    const float c = max_norm / (norm + 1e-6f);
+    out[0] = norm;
+    out[1] = c > 1.f ? 1.f : c;
+    if ((__float_as_uint(norm) & 0x7f800000u) == 0x7f800000u) *flag = 1.f;
+  }
 }
 
 // The fp16 flavour's gradient scale of one engine backward (engine.GradStore.begin_scaled) in ONE launch: S = 2^floor(log2(target / max|g|))
@@ -159,9 +239,37 @@ extern "C" int pvrl_nonfinite_flag_f32(const float* x, int64_t n, float* flag, v
   return PVRL_OK;
 }
 
-extern "C" int pvrl_adam_step(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1,
-                              double beta2, double eps, double weight_decay, int64_t step, double gscale, int decoupled,
-                              const float* skip, void* stream) {
+// workgroups of sumsq_kernel for n elements = fp64 slots one pvrl_sumsq_f32 call writes (nonfinite_kernel's grid)
+static long sumsq_blocks(long n) {
+  long blocks = (n / 4 + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  return blocks;
+}
+
+extern "C" int64_t pvrl_sumsq_slots(int64_t n) { return n <= 0 ? 0 : sumsq_blocks((long)n); }
+
+extern "C" int pvrl_sumsq_f32(const float* g, int64_t n, void* ws, int64_t slot, int64_t ws_slots, float* flag, void* stream) {
+  if (n <= 0) return PVRL_OK;
+  if (!g || !ws || !flag || ((uintptr_t)g & 15) || ((uintptr_t)ws & 7)) return PVRL_EINVAL;
+  const long blocks = sumsq_blocks((long)n);
+  if (slot < 0 || slot + blocks > ws_slots) return PVRL_EINVAL;          // the call would write behind the workspace
+  hipLaunchKernelGGL(sumsq_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g, (long)n, (double*)ws + slot, flag);
+  PVRL_LAUNCH_CHECK();
+  return PVRL_OK;
+}
+
+extern "C" int pvrl_clip_coef(const void* ws, int64_t nslots, double gscale, double max_norm, float* out, float* flag, void* stream) {
+  if (!ws || !out || !flag || ((uintptr_t)ws & 7) || nslots < 0 || !(max_norm > 0.0)) return PVRL_EINVAL;
+  hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)ws, (long)nslots, (float)gscale,
+                     (float)max_norm, out, flag);
+  PVRL_LAUNCH_CHECK();
+  return PVRL_OK;
+}
+
+extern "C" int pvrl_adam_step_clip(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1,
+                                   double beta2, double eps, double weight_decay, int64_t step, double gscale, int decoupled,
+                                   const float* skip, const float* clip, void* stream) {
   if (n <= 0) return PVRL_OK;
   if (!p || !g || !m || !v || step < 1) return PVRL_EINVAL;
   if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return PVRL_EINVAL;   // adam_kernel takes f32x4 loads
@@ -177,7 +285,30 @@ extern "C" int pvrl_adam_step(float* p, const float* g, float* m, float* v, int6
   long blocks = (n / 4 + 255) / 256;
   if (blocks > 0x7fffffffL) blocks = 0x7fffffffL;
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n, c, skip);
+  if (clip) hipLaunchKernelGGL(adam_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n, c, skip, clip);
+  else hipLaunchKernelGGL(adam_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n, c, skip, clip);
+  PVRL_LAUNCH_CHECK();
+  return PVRL_OK;
+}
+
+extern "C" int pvrl_adam_step(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1,
+                              double beta2, double eps, double weight_decay, int64_t step, double gscale, int decoupled,
+                              const float* skip, void* stream) {
+  return pvrl_adam_step_clip(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, gscale, decoupled, skip, nullptr, stream);
+}
+
+extern "C" int pvrl_sgd_step_clip(float* p, const float* g, float* buf, int64_t n, double lr, double momentum,
+                                  double dampening, double weight_decay, int nesterov, int first_step, double gscale,
+                                  const float* skip, const float* clip, void* stream) {
+  if (n <= 0) return PVRL_OK;
+  if (!p || !g || (momentum != 0.0 && !buf)) return PVRL_EINVAL;
+  long blocks = (n + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  const float mo = (float)momentum, omd = (float)(1.0 - dampening), wd = (float)weight_decay;
+  if (clip) hipLaunchKernelGGL(sgd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, buf, (long)n, (float)lr, mo, omd,
+                               wd, nesterov, first_step, (float)gscale, skip, clip);
+  else hipLaunchKernelGGL(sgd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, buf, (long)n, (float)lr, mo, omd,
+                          wd, nesterov, first_step, (float)gscale, skip, clip);
   PVRL_LAUNCH_CHECK();
   return PVRL_OK;
 }
@@ -185,12 +316,5 @@ extern "C" int pvrl_adam_step(float* p, const float* g, float* m, float* v, int6
 extern "C" int pvrl_sgd_step(float* p, const float* g, float* buf, int64_t n, double lr, double momentum,
                              double dampening, double weight_decay, int nesterov, int first_step, double gscale,
                              const float* skip, void* stream) {
-  if (n <= 0) return PVRL_OK;
-  if (!p || !g || (momentum != 0.0 && !buf)) return PVRL_EINVAL;
-  long blocks = (n + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(sgd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, buf, (long)n, (float)lr,
-                     (float)momentum, (float)(1.0 - dampening), (float)weight_decay, nesterov, first_step, (float)gscale, skip);
-  PVRL_LAUNCH_CHECK();
-  return PVRL_OK;
+  return pvrl_sgd_step_clip(p, g, buf, n, lr, momentum, dampening, weight_decay, nesterov, first_step, gscale, skip, nullptr, stream);
 }

@@ -49,10 +49,22 @@ class FusedOptimizer(torch.optim.Optimizer):
         # The reference raises at the bad iteration; `train_epoch` at its next log point.
         # `check_grads` (default for the fp16-operand flavour, whose scaled backward can overflow where the loss cannot) additionally
         # scans the gradients of parameters whose producers do not check themselves (GradStore.fused_checked lists the others).
+        # It governs that separate scan only: with `clip_grad_l2norm > 0` the norm pass reads every gradient anyway and raises the flag on
+        # inf / nan whatever `check_grads` (PVRL_CHECK_GRADS=0) says -- a clipped step with a non-finite gradient is always dropped.
         self.check_grads = os.environ.get("PVRL_CHECK_GRADS", "1" if OPERAND == "f16" else "0") == "1"
         self.bad_steps = None      # device counter of dropped steps
         self._dropped_seen = 0     # ... as of the last dropped_steps() call
         self._pending_idx = None   # parameters that had a gradient in EVERY step() since then (None: no step yet)
+        # Global-norm clipping (SOLVER.CLIP_GRAD_L2NORM; 0 = off), torch.nn.utils.clip_grad_norm_ without its host-visible scalar and
+        # without its rescaling pass: one streaming pass per contiguous run of the gradients of ALL parameter groups leaves fp64 partial
+        # sums of squares in `_clip_ws`, one small kernel turns them into {norm, coefficient} in `_clip_out`, and the update kernels
+        # multiply by the coefficient they read from there.  The norm is that of what the update applies (after `grad_scale`: the
+        # averaged gradient under accumulation and data parallelism, where upstream clips too); a parameter without a gradient is
+        # not part of it (torch skips `grad is None`).  The same pass raises the skip flag on inf / nan, so a clipped step launches
+        # no separate scan.  Nothing of this is optimiser state: state_dict() does not change.
+        self.clip_grad_l2norm = 0.0
+        self._clip_ws = None       # fp64 partial sums, sized once for the worst split into runs
+        self._clip_out = None      # [norm before clipping, coefficient] of the last clipped step
 
     @property
     def skip_flag(self):
@@ -78,6 +90,28 @@ class FusedOptimizer(torch.optim.Optimizer):
         self._dropped_seen = n
         self._pending_idx = None
         return n
+
+    def _clip_buffers(self):
+        gs = self.vt.grad_store()
+        if self._clip_out is None or self._clip_out.device != gs.flat.device:
+            L = lib()
+            # a run is a union of whole parameter spans (multiples of 64 elements) and the slot count is subadditive over them, so the
+            # per-parameter sum bounds every split into runs; pvrl_sumsq_f32 refuses a call that would write behind it
+            cap = sum(L.call("pvrl_sumsq_slots", gs.span(i)[1] - gs.span(i)[0]) for i in range(len(gs.params)))
+            self._clip_ws = torch.zeros(max(cap, 1), device=gs.flat.device, dtype=torch.float64)
+            self._clip_out = torch.tensor([0.0, 1.0], device=gs.flat.device)
+        return self._clip_ws, self._clip_out
+
+    @property
+    def grad_norm(self):
+        """1-element device view: the global gradient norm (after `grad_scale`, before clipping) of the last step() taken with
+        `clip_grad_l2norm > 0`; not finite when a gradient was inf / nan (a step dropped for a non-finite LOSS alone leaves it finite).  Reading it on the host is a sync: do it where the loop syncs anyway."""
+        return self._clip_buffers()[1][0:1]
+
+    @property
+    def clip_coef(self):
+        """1-element device view: min(1, clip_grad_l2norm / (grad_norm + 1e-6)), what the last clipped step multiplied its gradients by"""
+        return self._clip_buffers()[1][1:2]
 
     # -- flat storage -----------------------------------------------------------------------
     def _ensure_flat(self):
@@ -120,6 +154,9 @@ class FusedOptimizer(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         L = lib()
+        max_norm = float(self.clip_grad_l2norm)
+        if max_norm < 0.0:
+            raise ValueError(f"clip_grad_l2norm = {max_norm}: expected a norm > 0, or 0 for no clipping")
         gs0 = self.vt.grad_store()
         had_grad = [p.grad is not None for p in gs0.params]
         self.vt.adopt_grads(keep_none=True, zero_unused=bool(os.environ.get("PVRL_ZERO_UNUSED")))   # parameters without a gradient are skipped below, as torch.optim does (PVRL_ZERO_UNUSED=1: A/B switch, zero their slots anyway)
@@ -134,7 +171,16 @@ class FusedOptimizer(torch.optim.Optimizer):
         if self.bad_steps is None or self.bad_steps.device != gs.flat.device:
             self.bad_steps = torch.zeros(1, device=gs.flat.device)
         skip = vp(gs.bad.data_ptr())
-        if self.check_grads:       # gradients written by kernels that do not raise the flag themselves (head, glue, MViT engine)
+        clip = None
+        if max_norm > 0.0:         # the norm pass reads every gradient of this step and raises `skip` like the scan below, which it replaces
+            ws, out = self._clip_buffers()
+            slot = 0
+            for a, b, _ in self._runs(gs, gs.params, had_grad, by_step=False):      # (padding slots inside a run are zero: GradStore)
+                L.call("pvrl_sumsq_f32", vp(base_g + 4 * a), b - a, vp(ws.data_ptr()), slot, ws.numel(), skip, stream)
+                slot += L.call("pvrl_sumsq_slots", b - a)
+            L.call("pvrl_clip_coef", vp(ws.data_ptr()), slot, float(self.grad_scale), max_norm, vp(out.data_ptr()), skip, stream)
+            clip = vp(out.data_ptr() + 4)
+        elif self.check_grads:     # gradients written by kernels that do not raise the flag themselves (head, glue, MViT engine)
             # ... and, under data parallelism, EVERYTHING: what sits in the buffer now are sums over ranks (an overflow of the sum, an inf
             # from the 16-bit payload's staging), which no producer kernel has seen -- one ~0.1 ms pass
             scan_all = getattr(gs, "reduced_over_ranks", False)
@@ -145,15 +191,16 @@ class FusedOptimizer(torch.optim.Optimizer):
         for g in self.param_groups:
             for a, b, done in self._runs(gs, g["params"], had_grad):
                 n, o = b - a, 4 * a
+                tail = (skip, stream) if clip is None else (skip, clip, stream)     # clipping off: the entry points without `clip`
                 if self.method == "sgd":
-                    L.call("pvrl_sgd_step", vp(base_p + o), vp(base_g + o), vp(base_1 + o), n, float(g["lr"]),
-                           float(g["momentum"]), float(g["dampening"]), float(g["weight_decay"]),
-                           1 if g["nesterov"] else 0, 1 if done == 0 else 0, float(self.grad_scale), skip, stream)
+                    L.call("pvrl_sgd_step" if clip is None else "pvrl_sgd_step_clip", vp(base_p + o), vp(base_g + o), vp(base_1 + o), n,
+                           float(g["lr"]), float(g["momentum"]), float(g["dampening"]), float(g["weight_decay"]),
+                           1 if g["nesterov"] else 0, 1 if done == 0 else 0, float(self.grad_scale), *tail)
                 else:
-                    L.call("pvrl_adam_step", vp(base_p + o), vp(base_g + o), vp(base_1 + o), vp(base_2 + o), n,
-                           float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
+                    L.call("pvrl_adam_step" if clip is None else "pvrl_adam_step_clip", vp(base_p + o), vp(base_g + o), vp(base_1 + o),
+                           vp(base_2 + o), n, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
                            float(g["weight_decay"]), done + 1, float(self.grad_scale),
-                           1 if self.method == "adamw" else 0, skip, stream)
+                           1 if self.method == "adamw" else 0, *tail)
             for p in g["params"]:
                 i = gs.index.get(id(p))
                 if i is not None and had_grad[i]:
@@ -269,8 +316,13 @@ def construct_optimizer(model, cfg):
     s = cfg.SOLVER
     if s.OPTIMIZING_METHOD not in ("sgd", "adam", "adamw"):
         raise NotImplementedError("Does not support {} optimizer".format(s.OPTIMIZING_METHOD))
-    return FusedOptimizer(optim_params, model, s.OPTIMIZING_METHOD, lr=s.BASE_LR, momentum=s.MOMENTUM,
-                          dampening=s.DAMPENING, nesterov=s.NESTEROV, weight_decay=s.WEIGHT_DECAY)
+    clip = float(s.CLIP_GRAD_L2NORM)
+    if clip < 0.0:
+        raise ValueError(f"SOLVER.CLIP_GRAD_L2NORM = {clip}: expected a norm > 0, or 0.0 for no clipping")
+    opt = FusedOptimizer(optim_params, model, s.OPTIMIZING_METHOD, lr=s.BASE_LR, momentum=s.MOMENTUM,
+                         dampening=s.DAMPENING, nesterov=s.NESTEROV, weight_decay=s.WEIGHT_DECAY)
+    opt.clip_grad_l2norm = clip    # global-norm clipping inside step() (upstream SlowFast's key; its MViTv2 recipes train with 1.0)
+    return opt
 
 
 def get_epoch_lr(cur_epoch, cfg):

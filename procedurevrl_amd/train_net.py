@@ -186,8 +186,12 @@ def train_epoch(train_loader, model, optimizer, reducer, cur_epoch, cfg, max_ite
             w = torch.stack(window)
             # one host sync per LOG_PERIOD: the medians, "every loss of the window is finite", "no step of the window was skipped"
             drops = optimizer.bad_steps if getattr(optimizer, "bad_steps", None) is not None else torch.zeros(1, device=w.device)
+            # ... and, with SOLVER.CLIP_GRAD_L2NORM on, the gradient norm of the last step: it rides in the same transfer
+            clipping = getattr(optimizer, "clip_grad_l2norm", 0.0) > 0.0
+            gnorm = [optimizer.grad_norm.to(w.device).view(1)] if clipping else []
             vals = torch.cat([w.median(0).values, w[:, 0].isfinite().all().float().view(1),
-                              (drops.to(w.device) - dropped_before).view(1)]).tolist()
+                              (drops.to(w.device) - dropped_before).view(1)] + gnorm).tolist()
+            grad_norm = vals.pop() if clipping else None
             finite, dropped = vals[-2], vals[-1]
             vals = vals[:-2]
             if finite == 0.0 or dropped != 0.0 or any(math.isnan(v) or math.isinf(v) for v in vals):
@@ -203,6 +207,8 @@ def train_epoch(train_loader, model, optimizer, reducer, cur_epoch, cfg, max_ite
                 m = vals
                 line.update({"verb_loss": m[3], "noun_loss": m[4], "verb_top1_acc": m[5], "verb_top5_acc": m[6],
                              "noun_top1_acc": m[7], "noun_top5_acc": m[8], "top1_acc": m[9], "top5_acc": m[10]})
+            if clipping:
+                line["grad_norm"] = grad_norm
             log_json_stats(line)
             last_line = line
             window = []
